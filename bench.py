@@ -9,7 +9,12 @@ corrupted over eleven reject/accept classes, seed 2 (+ rank).
 One "step" = one verify pass over the whole batch with its inputs already
 resident in HBM (bh_verify_dev: DER parse, checks, SHA-256, batched inversion,
 u1 G + u2 Q, bitmap): `value` is that rate, barrier + device sync around the
-K timed steps. The PCIe-inclusive rate SURVEY 8(d) also names for config 2
+K timed steps. A plain run measures that alone: it generates the batch, uploads
+it, warms up, times the K steps, checks the last outputs against the
+generator's expectation and prints the line (`--dump-outputs DIR` also writes
+those outputs). Everything else is `--full`'s: the host paths, the serialised
+per-kernel passes and the roofline, the CPU baselines, the side configs.
+With `--full` the PCIe-inclusive rate SURVEY 8(d) also names for config 2
 (H2D + verify + results to page-locked memory per step through
 bh_verify_submit from page-locked host buffers, four batches in flight, so
 batch k+1's upload runs under batch k's kernels) is measured first and reported beside it as `host_path`.
@@ -148,6 +153,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the host paths, "
+                         "the per-kernel times and roofline, the CPU baselines, the side configs "
+                         "(each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="configs 2 / 5: write what the last timed step returned (valid, reason) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--n", type=int, default=1 << 20, help="config 2: records per GPU")
     ap.add_argument("--n-total", type=int, default=CONFIG5_TOTAL,
                     help="config 5: records of the one batch split over all GPUs")
@@ -176,7 +188,7 @@ def parse(argv=None):
     ap.add_argument("--mac-peak", type=float, default=float(os.environ.get("BH_MAC_PEAK", 0) or 0),
                     help="measured v_mad_u64_u32 peak (MAC/s); default: profiles/ubench.json")
     ap.add_argument("--side-configs", type=int, default=1,
-                    help="default run: also measure configs 1, 3, 4 and the single Verify")
+                    help="--full, config 2: also measure configs 1, 3, 4 and the single Verify")
     ap.add_argument("--side-steps", type=int, default=20)
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise the launcher and the rank plumbing only")
@@ -185,7 +197,14 @@ def parse(argv=None):
                          "(default: <tmp>/bdls_c5_cache; 'off' disables)")
     ap.add_argument("--c5-cache-save", type=int, default=1,
                     help="config 5: write a freshly generated shard to the cache")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.hbm_resident and not a.full:
+        ap.error("--hbm-resident 0 times the host path, which is --full's")
+    if a.dump_outputs and a.config not in (2, 5):
+        ap.error("--dump-outputs covers the throughput configs (2 and 5)")
+    return a
 
 
 def mac_peak_default() -> tuple[float, str]:
@@ -703,6 +722,112 @@ def measure_e2e(a, L, w, n, flags, local, world, depth, h2d_gbps):
             }
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, rank: int, valid, reason) -> None:
+    """--dump-outputs: what a caller of the timed path got back from its last
+    step -- the per-record verdict (the bitmap, unpacked) and reason code --
+    as float32 <name>.npy (rank r > 0: <name>.rank<r>.npy). Outputs that would
+    pass 64 MB are cut to a fixed seeded sample of the records, whose indices
+    go to sample_index.npy (float64)."""
+    arrays = {"valid": valid, "reason": reason}
+    n = len(reason)
+    if n * 4 * len(arrays) > DUMP_MAX_BYTES:
+        m = (DUMP_MAX_BYTES - 4096) // (4 * len(arrays) + 8)  # room for the .npy headers
+        idx = np.unique(np.random.default_rng(0).integers(0, n, m))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    for name, v in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"),
+                v.astype(np.float64 if name == "sample_index" else np.float32))
+    phase(f"outputs of the last timed step written to {path}")
+
+
+def resident_passes(a, L, w, n, flags, local, world):
+    """The headline figure: the batch uploaded to HBM once, then warmup and
+    K timed bh_verify_dev passes rotating over the compute lanes
+    (BH_F_ANY_LANE; one output set per possible lane, so no in-flight pass
+    shares its outputs), barrier + device sync around the timed ones. Returns
+    the figures, step(k, flags) for further passes on the same buffers, the
+    device buffers to free, and the last timed step's (valid, reason)."""
+    from bdls_amd import _lib, dist
+    DA = _lib.DeviceArray
+    phase("resident: uploading the batch to HBM")
+    d = [DA.from_numpy(local, x) for x in (w.pub, w.sig, w.sig_off, w.sig_len, w.msg,
+                                           w.msg_off, w.msg_len)]
+    # one output set per in-flight pass: BH_F_ANY_LANE orders pass k + 4
+    # after pass k (bdls_hip.cpp any_lane ring), so 4 rotating sets are safe
+    outs_dev = [(DA(local, ((n + 63) // 64) * 8), DA(local, n)) for _ in range(MAX_LANES)]
+    db = _lib.BhBatch(*[x.ptr for x in d])
+    lane_flag = _lib.BH_F_ANY_LANE if a.resident_lanes else 0
+
+    def step(k, f=flags | lane_flag):
+        words, dreason = outs_dev[k % MAX_LANES]
+        _lib.check(L.bh_verify_dev(local, 0, ctypes.byref(db), n, f, words.ptr,
+                                   dreason.ptr, None, 0, None))
+    phase("resident: warmup passes")
+    for k in range(max(1, a.warmup)):
+        step(k)
+    _lib.check(L.bh_sync(local))
+    dist.barrier(world)
+    phase(f"resident: {a.steps} timed passes")
+    r0 = time.perf_counter()
+    for k in range(a.steps):
+        step(k)
+    _lib.check(L.bh_sync(local))
+    r1 = time.perf_counter()
+    phase(f"resident: {(r1 - r0) * 1e3 / a.steps:.2f} ms per pass")
+    r_el = dist.max_over_ranks(r1 - r0, world)
+    r_ok, last = True, None
+    # the output sets the timed passes wrote, the last step's set last
+    for k in range(max(0, a.steps - MAX_LANES), a.steps):
+        words, dreason = outs_dev[k % MAX_LANES]
+        rbits = np.unpackbits(words.to_numpy(np.uint64, (n + 63) // 64).view(np.uint8),
+                              bitorder="little")[:n].astype(bool)
+        last = (rbits, dreason.to_numpy(np.uint8, n))
+        r_ok = r_ok and bool((last[1] == w.reason).all()
+                             and (rbits == w.expected_valid).all())
+    resident = {"value": round(dist.sum_over_ranks(n, world) * a.steps / r_el, 1),
+                "ms_per_step": round(r_el * 1e3 / a.steps, 3), "parity": r_ok,
+                "lanes": lane_count() if a.resident_lanes else 1}
+    return resident, step, d + [y for pair in outs_dev for y in pair], last
+
+
+def headline(a, world, value, ms_per_step, scaling, desc, n, nkeys, corrupt, resident, parity_ok):
+    """The result line's fields that every throughput run prints."""
+    from bdls_amd import dist
+    return {
+        "metric": "P-256 ECDSA verifies/sec (fused SHA-256, bit-exact vs Go crypto/ecdsa + Fabric low-S)",
+        "value": round(value, 1),
+        "unit": "verifies/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (seeded P-256 keys/signatures, workload/gen.c)",
+        "config": {
+            "workload": desc,
+            "records_per_gpu": n, "records_total": dist.sum_over_ranks(n, world),
+            "msg_len": a.msg_len, "nkeys": nkeys, "corrupt_den": corrupt,
+            "parallelism": f"shard{world} (no collective)",
+            "value_is": ("HBM-resident: bh_verify_dev passes over inputs already in device "
+                         "memory (one pass = one step; consecutive passes rotate over the "
+                         "compute lanes, BH_F_ANY_LANE), barrier + device sync around the "
+                         "timed steps" if resident else
+                         "host C ABI BatchVerify (bh_verify_submit/wait) from page-locked host "
+                         "buffers: H2D + verify + results to page-locked memory per step (--hbm-resident 0)"),
+        },
+        "parity": parity_ok,
+    }
+
+
 def bench_throughput(a, rank, world, local):
     from bdls_amd import _lib, dist, workload
     if a.config == 5:
@@ -771,6 +896,22 @@ def bench_throughput(a, rank, world, local):
     t_gen = time.time() - t_gen
     phase(f"workload ready in {t_gen:.1f} s ({gen_info.get('source', 'generator')})")
     flags = _lib.BH_F_HASH_SHA256
+    if not a.full:
+        # a plain run: the headline figure alone (everything else is --full's)
+        resident, _, bufs, last = resident_passes(a, L, w, n, flags, local, world)
+        for x in bufs:
+            x.free()
+        parity_ok = dist.all_true(resident["parity"], world)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, rank, *last)
+        out = headline(a, world, resident["value"], resident["ms_per_step"], scaling, desc, n,
+                       nkeys, corrupt, resident, parity_ok)
+        out.update({"hbm_resident": resident, "gen_s": round(t_gen, 2),
+                    "workload_source": gen_info, "device": {"index": local, "why": dev_why}})
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        dist.finalize(world)
+        return 0 if parity_ok else 3
     hb = _lib.BhBatch(*[x.ctypes.data for x in (w.pub, w.sig, w.sig_off, w.sig_len, w.msg,
                                                 w.msg_off, w.msg_len)])
     # config 5's keys are all distinct: the compact layout would hold the whole
@@ -878,39 +1019,7 @@ def bench_throughput(a, rank, world, local):
     # serialised, each kernel alone on the device.
     resident = None
     if a.hbm_resident:
-        DA = _lib.DeviceArray
-        phase("resident: uploading the batch to HBM")
-        d = [DA.from_numpy(local, x) for x in (w.pub, w.sig, w.sig_off, w.sig_len, w.msg,
-                                               w.msg_off, w.msg_len)]
-        # one output set per in-flight pass: BH_F_ANY_LANE orders pass k + 4
-        # after pass k (bdls_hip.cpp any_lane ring), so 4 rotating sets are safe
-        outs_dev = [(DA(local, ((n + 63) // 64) * 8), DA(local, n)) for _ in range(MAX_LANES)]
-        db = _lib.BhBatch(*[x.ptr for x in d])
-        lane_flag = _lib.BH_F_ANY_LANE if a.resident_lanes else 0
-
-        def step(k, f=flags | lane_flag):
-            words, dreason = outs_dev[k % MAX_LANES]
-            _lib.check(L.bh_verify_dev(local, 0, ctypes.byref(db), n, f, words.ptr,
-                                       dreason.ptr, None, 0, None))
-        phase("resident: warmup passes")
-        for k in range(max(1, a.warmup)):
-            step(k)
-        _lib.check(L.bh_sync(local))
-        dist.barrier(world)
-        phase(f"resident: {a.steps} timed passes")
-        r0 = time.perf_counter()
-        for k in range(a.steps):
-            step(k)
-        _lib.check(L.bh_sync(local))
-        r1 = time.perf_counter()
-        phase(f"resident: {(r1 - r0) * 1e3 / a.steps:.2f} ms per pass")
-        r_el = dist.max_over_ranks(r1 - r0, world)
-        r_ok = True
-        for words, dreason in outs_dev[:min(MAX_LANES, a.steps)]:
-            rbits = np.unpackbits(words.to_numpy(np.uint64, (n + 63) // 64).view(np.uint8),
-                                  bitorder="little")[:n].astype(bool)
-            r_ok = r_ok and bool((dreason.to_numpy(np.uint8, n) == w.reason).all()
-                                 and (rbits == w.expected_valid).all())
+        resident, step, bufs, last = resident_passes(a, L, w, n, flags, local, world)
         # the per-kernel timing passes (serialised, not part of `value`)
         phase(f"resident: {a.steps} serialised passes (per-kernel HIP-event times)")
         _lib.check(L.bh_timing_begin(local))
@@ -921,13 +1030,14 @@ def bench_throughput(a, rank, world, local):
         t_el = time.perf_counter() - t_t0
         _lib.check(L.bh_timing_end(local, ctypes.byref(tm)))
         phase("resident: done")
-        parity_ok = parity_ok and r_ok
-        resident = {"value": round(dist.sum_over_ranks(n, world) * a.steps / r_el, 1),
-                    "ms_per_step": round(r_el * 1e3 / a.steps, 3), "parity": r_ok,
-                    "lanes": lane_count() if a.resident_lanes else 1,
-                    "serialised_ms_per_step": round(t_el * 1e3 / a.steps, 3)}
-        for x in d + [y for pair in outs_dev for y in pair]:
+        parity_ok = parity_ok and resident["parity"]
+        resident["serialised_ms_per_step"] = round(t_el * 1e3 / a.steps, 3)
+        for x in bufs:
             x.free()
+    else:
+        last = (bits, rs)  # the host path is the timed path
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, *last)
     parity_ok = dist.all_true(parity_ok, world)
     if e2e:
         # what bounds it: the longest per-batch stage of the three that overlap
@@ -958,32 +1068,9 @@ def bench_throughput(a, rank, world, local):
     fp_ops = kernel_fp_ops(dom, routes)
     achieved = fp_ops * MAC_PER_FP / dom_avg_s if dom_avg_s > 0 else 0.0
     kname = KERNELS[dom]
-    out = {
-        "metric": "P-256 ECDSA verifies/sec (fused SHA-256, bit-exact vs Go crypto/ecdsa + Fabric low-S)",
-        "value": round(value, 1),
-        "unit": "verifies/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (seeded P-256 keys/signatures, workload/gen.c)",
-        "config": {
-            "workload": desc,
-            "records_per_gpu": n, "records_total": dist.sum_over_ranks(n, world),
-            "msg_len": a.msg_len, "nkeys": nkeys, "corrupt_den": corrupt,
-            "parallelism": f"shard{world} (no collective)",
-            "value_is": ("HBM-resident: bh_verify_dev passes over inputs already in device "
-                         "memory (one pass = one step; consecutive passes rotate over the "
-                         "compute lanes, BH_F_ANY_LANE), barrier + device sync around the "
-                         "timed steps" if resident else
-                         "host C ABI BatchVerify (bh_verify_submit/wait) from page-locked host "
-                         "buffers: H2D + verify + results to page-locked memory per step (--hbm-resident 0)"),
-        },
-        "parity": parity_ok,
+    out = headline(a, world, value, ms_per_step, scaling, desc, n, nkeys, corrupt, resident,
+                   parity_ok)
+    out.update({
         "hbm_resident": resident,
         "host_path": {"value": round(host_value, 1), "ms_per_step": round(host_ms_per_step, 3),
                       "what": (("host C ABI BatchVerify (bh_verify_compact_submit / "
@@ -1042,7 +1129,7 @@ def bench_throughput(a, rank, world, local):
         "gen_s": round(t_gen, 2),
         "workload_source": gen_info,
         "device": {"index": local, "why": dev_why},
-    }
+    })
     # the whole step priced two ways: the F_p ops this engine actually runs
     # (key tables skip the S0 doublings), and SURVEY 8(d)'s fixed schedule S0
     # (3,200 F_p ops per verify whatever the route) -- the latter can exceed 1

@@ -90,11 +90,11 @@ def test_mspid_fixture():
 
 
 def test_mspid_fixture_matches_reference_files():
-    """When the reference is mounted (this container), the committed fixture must
-    equal what gen_golden.py extracts from msp/testdata/mspid."""
-    ca = "/root/reference/msp/testdata/mspid/cacerts/ca.example.com-cert.pem"
-    if not os.path.exists(ca):
-        pytest.skip("reference not mounted")
+    """The committed fixture must equal what gen_golden.py extracts from the
+    reference's msp/testdata/mspid CA certificate (a copy of the PEM file is
+    kept under tests/golden/mspid)."""
+    ca = os.path.join(os.path.dirname(__file__), "golden", "mspid", "cacerts",
+                      "ca.example.com-cert.pem")
     import importlib.util
     spec = importlib.util.spec_from_file_location(
         "gen_golden", os.path.join(os.path.dirname(__file__), "golden", "gen_golden.py"))

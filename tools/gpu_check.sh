@@ -11,6 +11,9 @@ ok_or_stop() {  # $1 = exit code, $2 = step; test failures (1) continue, faults 
   esac
 }
 STEPS="${STEPS:-ubench tests bench prof}"
+# the steps below read the whole line (host paths, per-kernel times, side configs)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
+C5_ARGS="--full ${C5_ARGS:-}"
 for s in $STEPS; do
   case "$s" in
     ubench) timeout -k 10 120 bdls_amd/lib/ubench > gpurun_out/ubench.json 2> gpurun_out/ubench.err; rc=$?; cat gpurun_out/ubench.json; ok_or_stop $rc ubench ;;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host-path timeline from a rocprofv3 --kernel-trace --memory-copy-trace run of
-bench.py (config 2, plain defaults): where each timed batch's upload starts
+bench.py --full (config 2, default switches): where each timed batch's upload starts
 and ends, where its pass ends, and the gaps between them.
 
   python3 tools/hostpath_timeline.py <trace dir> [--steps K] [--out summary.json]

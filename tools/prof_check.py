@@ -5,7 +5,8 @@ command, split by bench phase, against the line's `roofline.launch_ms`.
 
 usage: python tools/prof_check.py <kernel_trace.csv> <bench.json> <out.json>
 
-The bench runs, in order: the host path (warmup + 1 single + K timed batches
+The bench command is the `--full` one (a plain run has neither the roofline nor
+these phases). It runs, in order: the host path (warmup + 1 single + K timed batches
 over the compute lanes, so a kernel may share the GPU with another lane's),
 since round 6 the staged host path host_path_e2e (max(1, warmup) + 1 + K
 batches, when the line carries it), then the HBM-resident passes (warmup + K timed, rotating over the lanes), K more

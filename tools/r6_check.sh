@@ -15,7 +15,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 300 python -u __graft_entry__.py > $O/smoke.log 2>&1; rc=$?; tail -1 $O/smoke.log
   [ $rc -eq 0 ] || stop smoke $rc
 fi
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; rc=$?
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; rc=$?
 [ $rc -eq 0 ] || [ $rc -eq 3 ] || stop bench $rc
 python3 -c "
 import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
@@ -32,7 +32,7 @@ if [ "${PMC:-1}" = 1 ]; then
   grp="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE"
   tag=$(echo $grp | tr ' ' '_' | cut -c1-40)
   BH_LANES=1 BH_KEYS_FIRST=0 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv \
-    -d $O/pmc_$tag -o pmc -- python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 \
+    -d $O/pmc_$tag -o pmc -- python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 \
     --hbm-resident 0 --side-configs 0 > $O/pmc_$tag.log 2>&1; rc=$?
   [ $rc -eq 0 ] || [ $rc -eq 3 ] || stop pmc $rc
   python3 tools/pmc_summary.py $O $O/pmc_summary.json > $O/pmc_summary.txt 2>&1 || echo "pmc_summary failed"

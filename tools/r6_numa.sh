@@ -13,7 +13,7 @@ cat $O/gpu_numa.txt
 for node in 0 1; do
   cpus=$(cat /sys/devices/system/node/node$node/cpulist)
   for m in 0; do
-    BH_PACK_SPREAD=$m timeout -k 10 300 taskset -c $cpus python bench.py --steps 20 --warmup 5 \
+    BH_PACK_SPREAD=$m timeout -k 10 300 taskset -c $cpus python bench.py --full --steps 20 --warmup 5 \
       --cpu-baseline 0 --side-configs 0 > $O/bench_n${node}_m$m.json 2> $O/bench_n${node}_m$m.err
     rc=$?; [ $rc -eq 0 ] || [ $rc -eq 3 ] || { echo "STOP n$node m$m ($rc)"; tail -3 $O/bench_n${node}_m$m.err; exit $rc; }
     python3 -c "

@@ -8,7 +8,7 @@ O=gpurun_out/${OUT:-numa2}
 mkdir -p $O
 for pass in 1 2; do
   for m in 1 0; do
-    BH_PACK_NUMA=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-baseline 0 \
+    BH_PACK_NUMA=$m timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 \
       --side-configs 0 > $O/bench_numa${m}_p$pass.json 2> $O/bench_numa${m}_p$pass.err
     rc=$?; [ $rc -eq 0 ] || [ $rc -eq 3 ] || { echo "STOP numa$m ($rc)"; tail -3 $O/bench_numa${m}_p$pass.err; exit $rc; }
     python3 -c "

@@ -15,7 +15,7 @@ for m in 0 1 2; do
 done
 for pass in 1 2; do
   for m in 0 1 2; do
-    BH_PACK_SPREAD=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-baseline 0 \
+    BH_PACK_SPREAD=$m timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 \
       --side-configs 0 > $O/bench_m${m}_p$pass.json 2> $O/bench_m${m}_p$pass.err
     rc=$?; [ $rc -eq 0 ] || [ $rc -eq 3 ] || { echo "STOP bench m$m ($rc)"; exit $rc; }
     python3 -c "
