@@ -9,9 +9,15 @@ LIB  := bdls_amd/lib
 
 HDRS := $(wildcard $(CSRC)/*.h) include/bdls_hip.h
 
-all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so $(LIB)/csp_load
+all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so \
+     tests/native/build/libhostsim384.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
+	@mkdir -p $(LIB)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the P-384 pass (BH_CURVE_P384): a translation unit of its own
+$(LIB)/verify384_kernels.o: $(CSRC)/verify384_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -27,7 +33,7 @@ $(LIB)/fabric.o: $(CSRC)/fabric.cpp $(HDRS)
 	@mkdir -p $(LIB)
 	g++ -O2 -std=c++17 -fPIC -Wall -Wno-unknown-pragmas -c $< -o $@
 
-$(LIB)/libbdlship.so: $(LIB)/verify_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o
+$(LIB)/libbdlship.so: $(LIB)/verify_kernels.o $(LIB)/verify384_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 $(LIB)/libbdlsgen.so: bdls_amd/workload/gen.c
@@ -42,6 +48,10 @@ tests/native/build/libhostsim.so: tests/native/hostsim.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
 
+tests/native/build/libhostsim384.so: tests/native/hostsim384.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
+
 # build-kernel experiments (profiles/r02/exp_build): not part of `all`
 EXP_VARIANTS := base:
 exp:
@@ -49,7 +59,7 @@ exp:
 	@for v in $(EXP_VARIANTS); do n=$${v%%:*}; f=$$(echo $${v#*:} | tr '+' ' '); \
 	  $(HIPCC) $(HIPFLAGS) $$f -c $(CSRC)/verify_kernels.hip -o build/exp/vk_$$n.o && \
 	  $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libbdlship_$$n.so build/exp/vk_$$n.o \
-	    $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o -lpthread || exit 1; done
+	    $(LIB)/verify384_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o -lpthread || exit 1; done
 
 clean:
 	rm -rf $(LIB) tests/native/build

@@ -21,6 +21,7 @@ BH_F_HASH_SHA3_256 = 8
 BH_F_ANY_LANE = 16
 BH_CURVE_P256 = 0
 BH_CURVE_SECP256K1 = 1
+BH_CURVE_P384 = 2
 
 # Every symbol include/bdls_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -35,7 +36,7 @@ EXPORTS = (
     "bh_block_signatures_preverify_bft", "bh_fabric_block_preverify_refs", "bh_device_stats",
     "bh_verify_compact", "bh_verify_compact_submit",
     "bh_batch_verify", "bh_batch_verify_submit", "bh_batch_verify_ptrs",
-    "bh_batch_verify_ptrs_submit", "bh_pack_stats",
+    "bh_batch_verify_ptrs_submit", "bh_pack_stats", "bh_curve_key_bytes",
 )
 KEY_FULL = 255  # bh_keys_register status: registry full
 
@@ -160,6 +161,8 @@ def lib() -> ctypes.CDLL:
         L.bh_device_count.restype = i32
         L.bh_last_error.restype = ctypes.c_char_p
         L.bh_version.restype = ctypes.c_char_p
+        L.bh_curve_key_bytes.argtypes = [i32]
+        L.bh_curve_key_bytes.restype = i32
         L.bh_workspace_bytes.argtypes = [sz]
         L.bh_workspace_bytes.restype = sz
         L.bh_verify.argtypes = [i32, ctypes.POINTER(BhBatch), sz, u32, vp, vp]

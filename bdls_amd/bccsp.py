@@ -34,6 +34,11 @@ ERROR_REASONS = frozenset({R_EMPTY_SIG, R_EMPTY_DIGEST, R_DER, R_R_NONPOS, R_S_N
 
 P256_N = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
 P256_HALF_N = P256_N >> 1
+P384_N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFC7634D81F4372DDF581A0DB248B0A77AECEC196ACCC52973
+P384_HALF_N = P384_N >> 1
+# curve name -> (BH_CURVE_*, coordinate bytes, half order): bccsp/utils/ecdsa.go:26-31
+_CURVES = {"P-256": (_lib.BH_CURVE_P256, 32, P256_HALF_N),
+           "P-384": (_lib.BH_CURVE_P384, 48, P384_HALF_N)}
 
 # Go error strings (bccsp/sw/impl.go, bccsp/sw/ecdsa.go, bccsp/utils/ecdsa.go)
 _ERR_TEXT = {
@@ -42,8 +47,13 @@ _ERR_TEXT = {
     R_DER: "Failed verifing with opts [%s]: Failed unmashalling signature [failed unmashalling signature]",
     R_R_NONPOS: "Failed verifing with opts [%s]: Failed unmashalling signature [invalid signature, R must be larger than zero]",
     R_S_NONPOS: "Failed verifing with opts [%s]: Failed unmashalling signature [invalid signature, S must be larger than zero]",
-    R_HIGH_S: "Failed verifing with opts [%s]: Invalid S. Must be smaller than half the order [%s][" + str(P256_HALF_N) + "].",
+    R_HIGH_S: "Failed verifing with opts [%s]: Invalid S. Must be smaller than half the order [%s][%HALF%].",
 }
+
+
+def _err_text(reason: int, curve: str = "P-256") -> str:
+    """The Go error text; the high-S one carries the curve's half order."""
+    return _ERR_TEXT[reason].replace("%HALF%", str(_CURVES[curve][2]))
 
 
 class BCCSPError(Exception):
@@ -56,16 +66,23 @@ class BCCSPError(Exception):
 
 @dataclass(frozen=True)
 class ECDSAPublicKey:
-    """bccsp/sw/ecdsakey.go:72 ecdsaPublicKey (P-256 only on this provider)."""
+    """bccsp/sw/ecdsakey.go:72 ecdsaPublicKey: curve "P-256" or "P-384", the two
+    curves of the sw provider (bccsp/sw/conf.go:43-61)."""
     x: int
     y: int
     curve: str = "P-256"
 
-    def raw64(self) -> bytes:
-        if self.x < 0 or self.y < 0 or self.x.bit_length() > 256 or self.y.bit_length() > 256:
+    def raw(self) -> bytes:
+        """X || Y big-endian, 64 bytes (P-256) or 96 (P-384): a bh_batch.pub entry."""
+        cb = _CURVES[self.curve][1]
+        if self.x < 0 or self.y < 0 or self.x.bit_length() > 8 * cb or self.y.bit_length() > 8 * cb:
             # pointFromAffine rejects these; encode an off-curve marker the engine rejects
-            return b"\x00" * 64
-        return self.x.to_bytes(32, "big") + self.y.to_bytes(32, "big")
+            return b"\x00" * (2 * cb)
+        return self.x.to_bytes(cb, "big") + self.y.to_bytes(cb, "big")
+
+    def raw64(self) -> bytes:
+        assert self.curve == "P-256"
+        return self.raw()
 
     def symmetric(self) -> bool:
         return False
@@ -100,10 +117,23 @@ def _arr(a: np.ndarray) -> int:
     return a.ctypes.data if a.size else 0
 
 
+def batch_curve(keys: Sequence[ECDSAPublicKey]) -> int:
+    """The BH_CURVE_* of a batch's keys: all on one curve (P-256 when empty)."""
+    names = {k.curve for k in keys}
+    if len(names) > 1:
+        raise BCCSPError(-1, f"keys of one batch must be on one curve, got {sorted(names)}")
+    for name in names:
+        if name not in _CURVES:
+            raise BCCSPError(-1, f"Unsupported 'VerifyKey' curve [{name}]")
+        return _CURVES[name][0]
+    return _lib.BH_CURVE_P256
+
+
 def pack_records(keys: Sequence[ECDSAPublicKey], sigs: Sequence[bytes], msgs: Sequence[bytes]):
-    """SoA packing of a batch (host numpy buffers)."""
+    """SoA packing of a batch (host numpy buffers); its keys are on one curve."""
     n = len(keys)
-    pub = np.frombuffer(b"".join(k.raw64() for k in keys) or b"\0", dtype=np.uint8)
+    batch_curve(keys)
+    pub = np.frombuffer(b"".join(k.raw() for k in keys) or b"\0", dtype=np.uint8)
     sig_len = np.fromiter((len(s) for s in sigs), dtype=np.uint32, count=n)
     msg_len = np.fromiter((len(m) for m in msgs), dtype=np.uint32, count=n)
     sig_off = np.zeros(n, dtype=np.uint64)
@@ -116,7 +146,8 @@ def pack_records(keys: Sequence[ECDSAPublicKey], sigs: Sequence[bytes], msgs: Se
     return pub, sig, sig_off, sig_len, msg, msg_off, msg_len
 
 
-def verify_packed(pub, sig, sig_off, sig_len, msg, msg_off, msg_len, flags: int = 0):
+def verify_packed(pub, sig, sig_off, sig_len, msg, msg_off, msg_len, flags: int = 0,
+                  curve: int = _lib.BH_CURVE_P256):
     """Host-buffer batch through bh_verify. Returns (valid bool[n], reason u8[n])."""
     _lib.ensure_init()
     n = len(sig_len)
@@ -124,7 +155,7 @@ def verify_packed(pub, sig, sig_off, sig_len, msg, msg_off, msg_len, flags: int 
     reason = np.zeros(n or 1, dtype=np.uint8)
     b = BhBatch(_arr(pub), _arr(sig), _arr(sig_off), _arr(sig_len), _arr(msg), _arr(msg_off),
                 _arr(msg_len))
-    _lib.check(_lib.lib().bh_verify(_lib.BH_CURVE_P256, ctypes.byref(b), n, flags,
+    _lib.check(_lib.lib().bh_verify(curve, ctypes.byref(b), n, flags,
                                     bitmap.ctypes.data, reason.ctypes.data))
     valid = np.unpackbits(bitmap, bitorder="little")[:n].astype(bool)
     return valid, reason[:n]
@@ -154,12 +185,14 @@ class HipCSP:
     def verify(self, k, signature: bytes, digest: bytes, opts=None) -> bool:
         if k is None:
             raise BCCSPError(-1, "Invalid Key. It must not be nil.")
-        if not isinstance(k, ECDSAPublicKey) or k.curve != "P-256":
+        if not isinstance(k, ECDSAPublicKey) or k.curve not in _CURVES:
             raise BCCSPError(-1, f"Unsupported 'VerifyKey' provided [{k}]")
         sig, dg = bytes(signature or b""), bytes(digest or b"")
-        if self._flags:  # a no-low-S provider: plain one-record batch
-            valid, reason = verify_packed(*pack_records([k], [sig], [dg]), flags=self._flags)
-            return self._result(int(reason[0]), bool(valid[0]), opts)
+        # a no-low-S provider, or a P-384 key (no coalescer for it): a one-record batch
+        if self._flags or k.curve != "P-256":
+            valid, reason = verify_packed(*pack_records([k], [sig], [dg]), flags=self._flags,
+                                          curve=batch_curve([k]))
+            return self._result(int(reason[0]), bool(valid[0]), opts, k.curve)
         # bh_csp_verify_p256: concurrent callers share device passes (coalescer);
         # ctypes releases the GIL for the call
         v, r = ctypes.c_int(), ctypes.c_int()
@@ -167,9 +200,9 @@ class HipCSP:
                                                  ctypes.byref(v), ctypes.byref(r)))
         return self._result(r.value, bool(v.value), opts)
 
-    def _result(self, reason: int, valid: bool, opts) -> bool:
+    def _result(self, reason: int, valid: bool, opts, curve: str = "P-256") -> bool:
         if reason in ERROR_REASONS:
-            txt = _ERR_TEXT[reason]
+            txt = _err_text(reason, curve)
             if "%s" in txt:
                 txt = txt.replace("%s", str(opts), 1).replace("%s", "", 1)
             raise BCCSPError(reason, txt)
@@ -179,14 +212,15 @@ class HipCSP:
     def batch_verify(self, keys: Sequence[ECDSAPublicKey], signatures: Sequence[bytes],
                      digests: Sequence[bytes]):
         """Returns (valid bool[n], reason u8[n]); reason in ERROR_REASONS <=> Go error."""
-        return verify_packed(*pack_records(keys, signatures, digests), flags=self._flags)
+        return verify_packed(*pack_records(keys, signatures, digests), flags=self._flags,
+                             curve=batch_curve(keys))
 
     def batch_identity_verify(self, keys: Sequence[ECDSAPublicKey], messages: Sequence[bytes],
                               signatures: Sequence[bytes], family: str = "SHA2"):
         """msp/identities.go:170-199 for a whole batch with the MSP's hash family
         (SHA2 -> SHA-256, SHA3 -> SHA3-256) fused on device."""
         return verify_packed(*pack_records(keys, signatures, messages),
-                             flags=self._flags | family_flag(family))
+                             flags=self._flags | family_flag(family), curve=batch_curve(keys))
 
     def identity_verify(self, k, msg: bytes, sig: bytes, family: str = "SHA2") -> None:
         """identity.Verify: raises on error or invalid signature (returns None if valid)."""
@@ -194,7 +228,7 @@ class HipCSP:
         r = int(reason[0])
         if r in ERROR_REASONS:
             raise BCCSPError(r, "could not determine the validity of the signature: " +
-                             _ERR_TEXT[r].replace("%s", "<nil>", 1).replace("%s", "", 1))
+                             _err_text(r, k.curve).replace("%s", "<nil>", 1).replace("%s", "", 1))
         if not valid[0]:
             raise BCCSPError(r, "The signature is invalid")
 

@@ -28,6 +28,7 @@
 
 #include "../../include/bdls_hip.h"
 #include "verify.h"
+#include "verify384.h"
 #include "pack.h"
 #include "shard.h"
 
@@ -45,6 +46,9 @@ hipError_t launch_small(int curve, const BatchIn& in, const Work& w, const KeyRe
                         uint32_t bs);
 hipError_t launch_register(int curve, const uint8_t* pub, const Work& w, const Plan& pl,
                            const KeyReg& g, uint32_t n, uint8_t* status, hipStream_t s);
+hipError_t launch_gtab384_build(uint32_t* gtab, hipStream_t s);
+hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* gtab, uint32_t n,
+                            uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev);
 size_t expand_temp_bytes(uint32_t m);
 hipError_t launch_result_out(const void* src, void* host_dst, size_t bytes, hipStream_t s);
 hipError_t launch_expand(const uint8_t* keys, const uint32_t* key_idx, uint8_t* pub,
@@ -213,6 +217,11 @@ struct Dev {
   hipStream_t aux = nullptr;     // BDLS digests beside the rest of a pass
   hipEvent_t fork = nullptr, join = nullptr;
   uint32_t* gtab[2] = {nullptr, nullptr};
+  // BH_CURVE_P384 (allocated and built at the device's first P-384 call, under mu)
+  uint32_t* gtab384 = nullptr;  // fixed-base table of G
+  DevBuf ws384;                 // Work384
+  DevBuf in384, out384;         // bh_verify: one chunk's inputs / bitmap words + reasons
+  hipEvent_t ev384[4] = {nullptr, nullptr, nullptr, nullptr};
   DevBuf ws;     // Work + Plan
   DevBuf stage;  // key registration input
   DevBuf out;    // key registration status
@@ -475,6 +484,15 @@ void dev_free(Dev& d) {
   if (d.copy) (void)hipStreamSynchronize(d.copy);
   for (auto& g : d.gtab)
     if (g) (void)hipFree(g);
+  if (d.gtab384) (void)hipFree(d.gtab384);
+  d.gtab384 = nullptr;
+  d.ws384.release();
+  d.in384.release();
+  d.out384.release();
+  for (auto& e : d.ev384) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
   d.ws.release();
   d.stage.release();
   d.out.release();
@@ -1658,7 +1676,18 @@ int submit_staged(int curve, const Src& src, size_t n, uint32_t flags, uint8_t* 
   return BH_OK;
 }
 
+// Entry point `fn` does not take `curve` (it serves BH_CURVE_P256 only).
+int curve_unsupported(int curve, const char* fn) {
+  if (curve == BH_CURVE_P384)
+    return fail(BH_E_INVALID, std::string("curve P-384 (BH_CURVE_P384) not supported by ") + fn +
+                                  ": use bh_verify or bh_verify_dev");
+  return fail(BH_E_INVALID, std::string("curve not supported by ") + fn);
+}
+
 int check_curve(int curve) {
+  if (curve == BH_CURVE_P384)
+    return fail(BH_E_INVALID, "curve P-384 (BH_CURVE_P384) not supported here: the BDLS and key "
+                              "registry entry points take BH_CURVE_P256 or BH_CURVE_SECP256K1");
   if (curve != BH_CURVE_P256 && curve != BH_CURVE_SECP256K1)
     return fail(BH_E_INVALID, "unknown curve");
   return BH_OK;
@@ -1670,6 +1699,182 @@ int check_flags(uint32_t flags) {
   if (flags & ~known) return fail(BH_E_INVALID, "unknown flag");
   if ((flags & BH_F_HASH_SHA256) && (flags & BH_F_HASH_SHA3_256))
     return fail(BH_E_INVALID, "BH_F_HASH_SHA256 and BH_F_HASH_SHA3_256 are exclusive");
+  return BH_OK;
+}
+
+// ---- BH_CURVE_P384 -------------------------------------------------------------
+// Records per pass: BH_P384_CHUNK (parsed once, rounded up to 64 so the bitmap
+// words of consecutive passes concatenate), default 65536: the workspace is
+// 1,777 bytes per record, most of it the per-record table of 1Q..8Q.
+size_t p384_chunk() {
+  static const size_t chunk = [] {
+    const char* e = getenv("BH_P384_CHUNK");
+    const long x = e ? atol(e) : 0L;
+    return x > 0 ? std::min(size_t(1) << 20, round64((size_t)x)) : size_t(1) << 16;
+  }();
+  return chunk;
+}
+
+// Workspace and G table of the device's P-384 pass (caller holds d.mu, device set).
+int p384_setup(Dev& d, size_t m, bh::Work384* w) {
+  if (!d.gtab384) {
+    uint32_t* g = nullptr;
+    hipError_t e = hipMalloc(&g, bh::kGTab384Words * 4);
+    if (e != hipSuccess) return fail(BH_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    // built on the device's own stream and waited for here, once: later passes
+    // on any stream find it complete
+    e = bh::launch_gtab384_build(g, d.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {
+      (void)hipFree(g);
+      return fail(BH_E_DEVICE, std::string("P-384 G table: ") + hipGetErrorString(e));
+    }
+    // the stage events first: gtab384 is published only with everything a pass needs
+    for (auto& ev : d.ev384) {
+      if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) {
+        ev = nullptr;
+        (void)hipFree(g);
+        return fail(BH_E_DEVICE, std::string("hipEventCreate: ") + hipGetErrorString(e));
+      }
+    }
+    d.gtab384 = g;
+  }
+  const size_t ns = round64(m);
+  if (int rc = d.ws384.ensure(ns * (bh::kWork384Words * 4 + 1) + 256 * 10)) return rc;
+  char* p = (char*)d.ws384.p;
+  auto take = [&](size_t bytes) {
+    char* q = p;
+    p += round256(bytes);
+    return q;
+  };
+  w->ns = (uint32_t)ns;
+  w->e = (uint32_t*)take(48 * ns);
+  w->r = (uint32_t*)take(48 * ns);
+  w->sm = (uint32_t*)take(56 * ns);
+  w->pre = (uint32_t*)take(56 * ns);
+  w->qx = (uint32_t*)take(56 * ns);
+  w->qy = (uint32_t*)take(56 * ns);
+  w->rm = (uint32_t*)take(56 * ns);
+  w->r2m = (uint32_t*)take(56 * ns);
+  w->qtab = (uint32_t*)take((size_t)8 * 3 * 56 * ns);
+  w->st = (uint8_t*)take(ns);
+  return BH_OK;
+}
+
+// The P-384 passes of a device-resident batch on stream s, after every lane's
+// work (one workspace per device). Caller holds d.mu, device set, and counts
+// the batch for bh_device_stats (one per call of the C ABI).
+int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bitmap,
+               uint8_t* reason, hipStream_t s, bh_timing* t) {
+  if (t) *t = bh_timing{};
+  const size_t chunk = p384_chunk();
+  for (size_t base = 0; base < n; base += chunk) {
+    const size_t m = std::min(chunk, n - base);
+    bh::Work384 w;
+    // the workspace may be reallocated: everything that used it has to be done
+    if (int rc = sync_lanes(d)) return rc;
+    if (round64(m) * (bh::kWork384Words * 4 + 1) + 2560 > d.ws384.cap)
+      HIPCHK(hipDeviceSynchronize());
+    if (int rc = p384_setup(d, m, &w)) return rc;
+    HIPCHK(wait_lanes(d, s));
+    const bh::In384 in{b->pub + base * 96, b->sig,     b->sig_off + base, b->sig_len + base,
+                       b->msg,             b->msg_off + base, b->msg_len + base,
+                       flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256)};
+    HIPCHK(bh::launch_verify384(in, w, d.gtab384, (uint32_t)m, bitmap + base / 64, reason + base,
+                                s, t ? d.ev384 : nullptr));
+    if (t) {
+      HIPCHK(hipEventSynchronize(d.ev384[3]));
+      float ms[3];
+      for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], d.ev384[k], d.ev384[k + 1]));
+      t->prep_ms += ms[0];
+      t->inv_ms += ms[1];
+      t->build_ladder_ms += ms[2];
+      t->n_ladder += (uint32_t)m;
+    }
+  }
+  HIPCHK(hipEventRecord(d.done, s));
+  d.done_recorded = true;
+  return BH_OK;
+}
+
+// bh_verify for BH_CURVE_P384: the first initialised device alone; upload, run
+// and download chunk by chunk, synchronously.
+int host_verify384(const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+                   uint8_t* reason) {
+  std::vector<Dev*> ds = all_devs();
+  if (ds.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
+  Dev& d = *ds[0];
+  if (n == 0) return BH_OK;
+  std::lock_guard<std::mutex> g(d.mu);
+  HIPCHK(hipSetDevice(d.id));
+  hipStream_t s = d.stream;
+  const size_t chunk = p384_chunk();
+  g_dev_batches.fetch_add(1, std::memory_order_relaxed);  // one batch, however many chunks
+  g_dev_records.fetch_add(n, std::memory_order_relaxed);
+  std::vector<uint64_t> so, mo, words;
+  for (size_t base = 0; base < n; base += chunk) {
+    const size_t m = std::min(chunk, n - base);
+    // the byte spans this chunk's records reference, rebased to the upload
+    auto span = [&](const uint64_t* off, const uint32_t* len, std::vector<uint64_t>& o,
+                    uint64_t* lo_out) -> size_t {
+      uint64_t lo = UINT64_MAX, hi = 0;
+      for (size_t i = base; i < base + m; i++) {
+        if (!len[i]) continue;
+        lo = std::min(lo, off[i]);
+        hi = std::max(hi, off[i] + len[i]);
+      }
+      if (lo == UINT64_MAX) lo = hi = 0;
+      o.resize(m);
+      for (size_t i = 0; i < m; i++) o[i] = len[base + i] ? off[base + i] - lo : 0;
+      *lo_out = lo;
+      return (size_t)(hi - lo);
+    };
+    uint64_t slo = 0, mlo = 0;
+    const size_t sbytes = span(b->sig_off, b->sig_len, so, &slo);
+    const size_t mbytes = span(b->msg_off, b->msg_len, mo, &mlo);
+    if ((sbytes && !b->sig) || (mbytes && !b->msg)) return fail(BH_E_INVALID, "null pointer in batch");
+    if (int rc = sync_lanes(d)) return rc;
+    HIPCHK(hipStreamSynchronize(s));  // the staging below is reused chunk after chunk
+    const size_t total = round256(m * 96) + 2 * round256(m * 8) + 2 * round256(m * 4) +
+                         round256(sbytes + 8) + round256(mbytes + 8);
+    if (int rc = d.in384.ensure(total)) return rc;
+    if (int rc = d.out384.ensure(round256(round64(m) / 8) + round256(m))) return rc;
+    char* p = (char*)d.in384.p;
+    auto put = [&](const void* src, size_t bytes, size_t reserve) -> char* {
+      char* q = p;
+      p += round256(reserve);
+      if (bytes && hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return nullptr;
+      return q;
+    };
+    bh_batch db;
+    char* q;
+    if (!(q = put(b->pub + base * 96, m * 96, m * 96))) return fail(BH_E_DEVICE, "P-384 upload");
+    db.pub = (const uint8_t*)q;
+    if (!(q = put(so.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "P-384 upload");
+    db.sig_off = (const uint64_t*)q;
+    if (!(q = put(mo.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "P-384 upload");
+    db.msg_off = (const uint64_t*)q;
+    if (!(q = put(b->sig_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "P-384 upload");
+    db.sig_len = (const uint32_t*)q;
+    if (!(q = put(b->msg_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "P-384 upload");
+    db.msg_len = (const uint32_t*)q;
+    if (!(q = put(sbytes ? b->sig + slo : nullptr, sbytes, sbytes + 8)))
+      return fail(BH_E_DEVICE, "P-384 upload");
+    db.sig = (const uint8_t*)q;
+    if (!(q = put(mbytes ? b->msg + mlo : nullptr, mbytes, mbytes + 8)))
+      return fail(BH_E_DEVICE, "P-384 upload");
+    db.msg = (const uint8_t*)q;
+    uint64_t* dbm = (uint64_t*)d.out384.p;
+    uint8_t* drs = (uint8_t*)d.out384.p + round256(round64(m) / 8);
+    if (int rc = run_dev384(d, &db, m, flags, dbm, drs, s, nullptr)) return rc;
+    words.resize(round64(m) / 64);
+    HIPCHK(hipMemcpyAsync(words.data(), dbm, words.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(reason + base, drs, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // base is a multiple of 64: whole bytes of the caller's LSB-first bitmap
+    for (size_t i = 0; i < (m + 7) / 8; i++)
+      bitmap[base / 8 + i] = (uint8_t)(words[i / 8] >> (8 * (i % 8)));
+  }
   return BH_OK;
 }
 
@@ -2094,6 +2299,15 @@ int bh_device_count(void) {
   return (int)g_devs.size();
 }
 
+int bh_curve_key_bytes(int curve) {
+  switch (curve) {
+    case BH_CURVE_P256:
+    case BH_CURVE_SECP256K1: return 64;
+    case BH_CURVE_P384: return 96;
+  }
+  return -1;
+}
+
 size_t bh_workspace_bytes(size_t n) { return work_bytes(round64(std::min(n, max_chunk()))); }
 
 int bh_verify_dev(int device, int curve, const bh_batch* b, size_t n, uint32_t flags,
@@ -2102,13 +2316,24 @@ int bh_verify_dev(int device, int curve, const bh_batch* b, size_t n, uint32_t f
   if (!b || (n && (!b->pub || !b->sig || !b->sig_off || !b->sig_len || !b->msg ||
                    !b->msg_off || !b->msg_len || !bitmap_words || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
-  if (curve != BH_CURVE_P256) return fail(BH_E_INVALID, "curve not supported by bh_verify_dev");
+  if (curve != BH_CURVE_P256 && curve != BH_CURVE_P384)
+    return curve_unsupported(curve, "bh_verify_dev");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   Dev* d = get_dev(device);
   if (!d) return fail(BH_E_NOT_INIT, "device not initialised (call bh_init)");
   std::lock_guard<std::mutex> g(d->mu);
   HIPCHK(hipSetDevice(d->id));
+  if (curve == BH_CURVE_P384) {  // BH_F_KEEP_KEYS / BH_F_ANY_LANE: ignored for this curve
+    hipStream_t s384 = stream ? (hipStream_t)stream : d->stream;
+    if (timing) *timing = bh_timing{};
+    if (n == 0) return BH_OK;
+    g_dev_batches.fetch_add(1, std::memory_order_relaxed);
+    g_dev_records.fetch_add(n, std::memory_order_relaxed);
+    if (int rc = run_dev384(*d, b, n, flags, bitmap_words, reason, s384, timing)) return rc;
+    if (sync && !timing) HIPCHK(hipStreamSynchronize(s384));
+    return BH_OK;
+  }
   // BH_F_ANY_LANE: rotate over the compute lanes like host batches (run_dev
   // orders the pass after its lane's previous one only)
   int lane = -1;
@@ -2134,9 +2359,11 @@ int bh_verify(int curve, const bh_batch* b, size_t n, uint32_t flags, uint8_t* b
   if (!b || (n && (!b->pub || !b->sig_off || !b->sig_len || !b->msg_off || !b->msg_len ||
                    !bitmap || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
-  if (curve != BH_CURVE_P256) return fail(BH_E_INVALID, "curve not supported by bh_verify");
+  if (curve != BH_CURVE_P256 && curve != BH_CURVE_P384)
+    return curve_unsupported(curve, "bh_verify");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
+  if (curve == BH_CURVE_P384) return host_verify384(b, n, flags, bitmap, reason);
   return host_verify(curve, b, n, flags, bitmap, reason);
 }
 
@@ -2146,7 +2373,7 @@ int bh_verify_2seg(int curve, const bh_batch* b, const uint64_t* msg2_off,
   if (!b || (n && (!b->pub || !b->sig_off || !b->sig_len || !b->msg_off || !b->msg_len ||
                    !msg2_off || !msg2_len || !bitmap || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
-  if (curve != BH_CURVE_P256) return fail(BH_E_INVALID, "curve not supported by bh_verify_2seg");
+  if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_2seg");
   if (int rc = check_flags(flags)) return rc;
   if (!(flags & (BH_F_HASH_SHA256 | BH_F_HASH_SHA3_256)))
     return fail(BH_E_INVALID, "bh_verify_2seg hashes on the device: pass BH_F_HASH_SHA256 or "
@@ -2163,7 +2390,7 @@ int bh_verify_submit(int curve, const bh_batch* b, size_t n, uint32_t flags, uin
   if (!b || (n && (!b->pub || !b->sig_off || !b->sig_len || !b->msg_off || !b->msg_len ||
                    !bitmap || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
-  if (curve != BH_CURVE_P256) return fail(BH_E_INVALID, "curve not supported by bh_verify_submit");
+  if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_submit");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   return submit_job(curve, b, n, flags, bitmap, reason, job);
@@ -2187,7 +2414,7 @@ static int check_compact(const bh_cbatch* b, size_t n, const uint8_t* bitmap,
 
 int bh_verify_compact(int curve, const bh_cbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
                       uint8_t* reason) {
-  if (curve != BH_CURVE_P256) return fail(BH_E_INVALID, "curve not supported by bh_verify_compact");
+  if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_compact");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   if (int rc = check_compact(b, n, bitmap, reason)) return rc;
@@ -2199,8 +2426,7 @@ int bh_verify_compact_submit(int curve, const bh_cbatch* b, size_t n, uint32_t f
                              uint8_t* bitmap, uint8_t* reason, bh_job** job) {
   if (!job) return fail(BH_E_INVALID, "null job");
   *job = nullptr;
-  if (curve != BH_CURVE_P256)
-    return fail(BH_E_INVALID, "curve not supported by bh_verify_compact_submit");
+  if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_compact_submit");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   if (int rc = check_compact(b, n, bitmap, reason)) return rc;
@@ -2210,7 +2436,7 @@ int bh_verify_compact_submit(int curve, const bh_cbatch* b, size_t n, uint32_t f
 
 // ---- staged BatchVerify (pack.h) ----
 static int check_staged(int curve, uint32_t flags, size_t n) {
-  if (curve != BH_CURVE_P256) return fail(BH_E_INVALID, "curve not supported by bh_batch_verify");
+  if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_batch_verify");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   return BH_OK;

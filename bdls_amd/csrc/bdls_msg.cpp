@@ -494,6 +494,9 @@ extern "C" int bh_bdls_preverify(int curve, const uint8_t* msgs, const uint64_t*
                                  size_t n_participants, uint32_t flags,
                                  bh_bdls_msg_result* results, uint8_t* sp_reason, size_t sp_cap,
                                  size_t* sp_total) {
+  if (curve == BH_CURVE_P384)
+    return bh::host_fail(BH_E_INVALID, "curve P-384 (BH_CURVE_P384) not supported by "
+                                       "bh_bdls_preverify");
   if (curve != BH_CURVE_P256 && curve != BH_CURVE_SECP256K1)
     return bh::host_fail(BH_E_INVALID, "unknown curve");
   if (flags & ~(BH_BDLS_F_GIVEN_REASONS | BH_BDLS_F_NO_QUORUM))

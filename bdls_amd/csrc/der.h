@@ -21,10 +21,13 @@
 
 namespace bh {
 
-struct DerSig {
-  uint32_t r[8], s[8];  // magnitudes (little-endian limbs) when <= 256 bits
-  uint32_t r_big, s_big;  // 1 if the magnitude exceeds 32 bytes
+// NW: words of a magnitude (8 for the 256-bit curves, 12 for P-384).
+template <int NW>
+struct DerSigT {
+  uint32_t r[NW], s[NW];  // magnitudes (little-endian limbs) when <= 32 NW bits
+  uint32_t r_big, s_big;  // 1 if the magnitude exceeds 4 NW bytes
 };
+using DerSig = DerSigT<8>;
 
 // Returns 0 on success.
 BH_HD int der_tag_len(const uint8_t* b, uint32_t n, uint32_t* off, uint32_t* cls,
@@ -73,7 +76,8 @@ BH_HD int der_tag_len(const uint8_t* b, uint32_t n, uint32_t* off, uint32_t* cls
 
 // parseField for a *big.Int. sign: -1/0/+1. For positive values fills the
 // magnitude limbs (or *big = 1).
-BH_HD int der_int(const uint8_t* b, uint32_t n, uint32_t* off, int* sign, uint32_t mag[8],
+template <int NW>
+BH_HD int der_int(const uint8_t* b, uint32_t n, uint32_t* off, int* sign, uint32_t mag[NW],
                   uint32_t* big) {
   if (*off == n) return -1;  // sequence truncated
   uint32_t cls, cmp, tag, len;
@@ -89,7 +93,7 @@ BH_HD int der_int(const uint8_t* b, uint32_t n, uint32_t* off, int* sign, uint32
     if ((b0 == 0 && !(b1 & 0x80u)) || (b0 == 0xffu && (b1 & 0x80u))) return -1;
   }
 #pragma unroll
-  for (int i = 0; i < 8; i++) mag[i] = 0;
+  for (int i = 0; i < NW; i++) mag[i] = 0;
   *big = 0;
   if (b0 & 0x80u) {
     *sign = -1;
@@ -102,14 +106,14 @@ BH_HD int der_int(const uint8_t* b, uint32_t n, uint32_t* off, int* sign, uint32
   *sign = 1;
   uint32_t s0 = start + (b0 == 0 ? 1u : 0u);
   uint32_t L = start + len - s0;
-  if (L > 32) {
+  if (L > 4 * NW) {
     *big = 1;
     return 0;
   }
-  // right-align the L magnitude bytes into 32 big-endian byte slots
+  // right-align the L magnitude bytes into 4 NW big-endian byte slots
   const uint32_t end = start + len;  // one past the last byte
 #pragma unroll
-  for (int j = 0; j < 32; j++) {  // j = byte index from the least significant end
+  for (int j = 0; j < 4 * NW; j++) {  // j = byte index from the least significant end
     uint32_t v = 0;
     if ((uint32_t)j < L) v = b[end - 1 - j];
     mag[j >> 2] |= v << (8 * (j & 3));
@@ -118,7 +122,8 @@ BH_HD int der_int(const uint8_t* b, uint32_t n, uint32_t* off, int* sign, uint32
 }
 
 // Returns R_OK, R_DER, R_R_NONPOS or R_S_NONPOS (bccsp/utils/ecdsa.go:41-65).
-BH_HD uint8_t der_parse_sig(const uint8_t* b, uint32_t n, DerSig* o) {
+template <int NW>
+BH_HD uint8_t der_parse_sig(const uint8_t* b, uint32_t n, DerSigT<NW>* o) {
   uint32_t off = 0, cls, cmp, tag, len;
   if (n == 0) return R_DER;
   if (der_tag_len(b, n, &off, &cls, &cmp, &tag, &len)) return R_DER;
@@ -127,8 +132,8 @@ BH_HD uint8_t der_parse_sig(const uint8_t* b, uint32_t n, DerSig* o) {
   const uint8_t* in = b + off;
   uint32_t io = 0;
   int rs = 0, ss = 0;
-  if (der_int(in, len, &io, &rs, o->r, &o->r_big)) return R_DER;
-  if (der_int(in, len, &io, &ss, o->s, &o->s_big)) return R_DER;
+  if (der_int<NW>(in, len, &io, &rs, o->r, &o->r_big)) return R_DER;
+  if (der_int<NW>(in, len, &io, &ss, o->s, &o->s_big)) return R_DER;
   if (rs <= 0) return R_R_NONPOS;
   if (ss <= 0) return R_S_NONPOS;
   return R_OK;

@@ -75,11 +75,27 @@ extern "C" {
 
 #define BH_CURVE_P256 0
 #define BH_CURVE_SECP256K1 1
+#define BH_CURVE_P384 2 /* the sw provider's second NIST curve (bccsp/sw/conf.go:59-61,
+                           security level 384). Taken by bh_verify and bh_verify_dev only, with
+                           the semantics they have for P-256 (Go-asn1 DER, R, S > 0, low-S with
+                           P-384's half order, pointFromAffine, r, s < n, hashToNat, the x
+                           check) and the same BH_R_* codes, precedence and bitmap. Keys are
+                           96 bytes (X || Y, 48 each). BH_F_HASH_SHA256 / BH_F_HASH_SHA3_256 as
+                           for P-256 (identity.Verify hashes with the MSP's family whatever the
+                           key's curve, msp/identities.go:170-227); in digest mode any length
+                           >= 1: the leftmost 48 bytes, a shorter digest whole, one reduction
+                           mod n. BH_F_KEEP_KEYS and BH_F_ANY_LANE are ignored. Every other
+                           entry point answers BH_E_INVALID for this curve. */
+
+/* Bytes of one public key (X || Y) in bh_batch.pub for a curve: 64, 64, 96;
+ * negative for an unknown curve. */
+int bh_curve_key_bytes(int curve);
 
 /* One batch of verify records (structure of arrays). Host pointers for
  * bh_verify(), device pointers for bh_verify_dev(). */
 typedef struct bh_batch {
-  const uint8_t *pub;      /* n * 64 bytes: Q.x || Q.y, 32-byte big-endian each        */
+  const uint8_t *pub;      /* n * 64 bytes: Q.x || Q.y, 32-byte big-endian each (P-384:
+                              n * 96, 48-byte coordinates; bh_curve_key_bytes)           */
   const uint8_t *sig;      /* concatenated ASN.1 DER signatures                          */
   const uint64_t *sig_off; /* n byte offsets into sig                                    */
   const uint32_t *sig_len; /* n lengths (0 -> BH_R_EMPTY_SIG)                            */
@@ -140,7 +156,12 @@ size_t bh_workspace_bytes(size_t n);
 /* Host-memory batch: copies to the devices, shards [0,n) over all initialised
  * devices (contiguous ranges, no collective), gathers bitmap and reasons.
  * curve: BH_CURVE_P256 (the Fabric/BCCSP path; secp256k1 BDLS messages use
- * bh_verify_bdls). */
+ * bh_verify_bdls) or BH_CURVE_P384. A P-384 batch runs on the first
+ * initialised device alone, uploaded, verified and downloaded in chunks of
+ * BH_P384_CHUNK records (environment, read once, rounded up to 64; default
+ * 65536); the device's P-384 workspace and fixed-base table of G are made at
+ * its first P-384 call (bh_init's cost does not change). bh_device_stats
+ * counts such a call as one batch, however many chunks it runs in. */
 int bh_verify(int curve, const bh_batch *b, size_t n, uint32_t flags, uint8_t *bitmap,
               uint8_t *reason);
 
@@ -178,7 +199,9 @@ int bh_host_free(void *ptr);
  * are device pointers on `device`. Enqueued on `stream` (hipStream_t; NULL =
  * the library's stream for that device) and synchronised before return when
  * timing != NULL (then filled) or when sync != 0. bitmap_words: ceil(n/64)
- * uint64 words. */
+ * uint64 words. BH_CURVE_P384: passes of BH_P384_CHUNK records behind every
+ * lane's work; timing fills prep_ms, inv_ms and build_ladder_ms (ladder, u1 G
+ * and the x check), n_ladder = n. */
 int bh_verify_dev(int device, int curve, const bh_batch *b, size_t n, uint32_t flags,
                   uint64_t *bitmap_words, uint8_t *reason, void *stream, int sync,
                   bh_timing *timing);
