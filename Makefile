@@ -44,7 +44,9 @@ oracle:
 	$(MAKE) -C oracle
 
 # test-only host build of the device arithmetic (never linked into the product)
-tests/native/build/libhostsim.so: tests/native/hostsim.cpp $(HDRS)
+# (hostsim_prehashed.cpp includes hostsim.cpp and adds the prehashed BDLS entries)
+tests/native/build/libhostsim.so: tests/native_prehashed/hostsim_prehashed.cpp \
+                                  tests/native/hostsim.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
 

@@ -28,7 +28,8 @@ EXPORTS = (
     "bh_init", "bh_shutdown", "bh_device_count", "bh_last_error", "bh_version",
     "bh_workspace_bytes", "bh_verify", "bh_verify_2seg", "bh_verify_dev", "bh_csp_verify_p256",
     "bh_parse_der_sig", "bh_dev_alloc", "bh_dev_free", "bh_memcpy_h2d", "bh_memcpy_d2h",
-    "bh_sync", "bh_verify_bdls", "bh_verify_bdls_dev", "bh_keys_reserve", "bh_keys_register",
+    "bh_sync", "bh_verify_bdls", "bh_verify_bdls_dev", "bh_verify_bdls_prehashed_dev",
+    "bh_keys_reserve", "bh_keys_register",
     "bh_keys_clear", "bh_keys_count", "bh_timing_begin", "bh_timing_end", "bh_bdls_preverify",
     "bh_verify_submit", "bh_verify_wait", "bh_host_alloc", "bh_host_free", "bh_csp_stats",
     "bh_fabric_block_preverify", "bh_verify_x509", "bh_signature_sets_verify",
@@ -241,6 +242,8 @@ def lib() -> ctypes.CDLL:
         L.bh_verify_bdls_dev.argtypes = [i32, i32, ctypes.POINTER(BhBdlsBatch), sz, vp, vp, vp,
                                          i32, ctypes.POINTER(BhTiming)]
         L.bh_verify_bdls_dev.restype = i32
+        L.bh_verify_bdls_prehashed_dev.argtypes = L.bh_verify_bdls_dev.argtypes
+        L.bh_verify_bdls_prehashed_dev.restype = i32
         L.bh_dev_alloc.argtypes = [i32, sz, ctypes.POINTER(vp)]
         L.bh_dev_alloc.restype = i32
         L.bh_dev_free.argtypes = [i32, vp]

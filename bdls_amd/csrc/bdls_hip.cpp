@@ -582,7 +582,8 @@ bh::BatchIn slice(const bh_batch* b, size_t base, uint32_t flags) {
 }
 bh::BdlsIn slice(const bh_bdls_batch* b, size_t base, uint32_t flags) {
   return bh::BdlsIn{b->xy + base * 64, b->r, b->r_off + base, b->r_len + base,
-                    b->s, b->s_off + base, b->s_len + base, b->version + base,
+                    b->s, b->s_off + base, b->s_len + base,
+                    b->version ? b->version + base : nullptr,  // unused when prehashed
                     b->msg, b->msg_off + base, b->msg_len + base, flags};
 }
 // bh_verify_2seg: a bh_batch whose message i is msg[msg_off, +msg_len) ||
@@ -2647,12 +2648,15 @@ int bh_timing_end(int device, bh_timing* t) {
 }
 
 // ---- BDLS consensus messages (SignedProto.Verify) --------------------------
-int bh_verify_bdls_dev(int device, int curve, const bh_bdls_batch* b, size_t n,
-                       uint64_t* bitmap_words, uint8_t* reason, void* stream, int sync,
-                       bh_timing* timing) {
+// bh_verify_bdls_dev / bh_verify_bdls_prehashed_dev: iflags carries the
+// internal BHF_BDLS_PREHASHED bit to BdlsIn::flags (version is then unused).
+static int bdls_dev(int device, int curve, const bh_bdls_batch* b, size_t n,
+                    uint64_t* bitmap_words, uint8_t* reason, void* stream, int sync,
+                    bh_timing* timing, uint32_t iflags) {
+  const bool prehashed = (iflags & bh::BHF_BDLS_PREHASHED) != 0;
   if (!b || (n && (!b->xy || !b->r || !b->r_off || !b->r_len || !b->s || !b->s_off ||
-                   !b->s_len || !b->version || !b->msg || !b->msg_off || !b->msg_len ||
-                   !bitmap_words || !reason)))
+                   !b->s_len || (!b->version && !prehashed) || !b->msg || !b->msg_off ||
+                   !b->msg_len || !bitmap_words || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
   if (int rc = check_curve(curve)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
@@ -2662,10 +2666,23 @@ int bh_verify_bdls_dev(int device, int curve, const bh_bdls_batch* b, size_t n,
   HIPCHK(hipSetDevice(d->id));
   hipStream_t s = stream ? (hipStream_t)stream : d->stream;
   if (n == 0) return BH_OK;
-  int rc = run_dev(*d, curve, b, n, 0u, bitmap_words, reason, s, timing);
+  int rc = run_dev(*d, curve, b, n, iflags, bitmap_words, reason, s, timing);
   if (rc) return rc;
   if (sync && !timing) HIPCHK(hipStreamSynchronize(s));
   return BH_OK;
+}
+
+int bh_verify_bdls_dev(int device, int curve, const bh_bdls_batch* b, size_t n,
+                       uint64_t* bitmap_words, uint8_t* reason, void* stream, int sync,
+                       bh_timing* timing) {
+  return bdls_dev(device, curve, b, n, bitmap_words, reason, stream, sync, timing, 0u);
+}
+
+int bh_verify_bdls_prehashed_dev(int device, int curve, const bh_bdls_batch* b, size_t n,
+                                 uint64_t* bitmap_words, uint8_t* reason, void* stream, int sync,
+                                 bh_timing* timing) {
+  return bdls_dev(device, curve, b, n, bitmap_words, reason, stream, sync, timing,
+                  bh::BHF_BDLS_PREHASHED);
 }
 
 int bh_verify_bdls(int curve, const bh_bdls_batch* b, size_t n, uint8_t* bitmap,

@@ -31,6 +31,9 @@ enum : uint32_t {
   BHF_HASH_SHA256 = 1u,    // msg is a message: digest = SHA-256(msg) (identity.Verify)
   BHF_NO_LOW_S = 2u,       // skip Fabric's low-S rule (plain Go ecdsa.Verify semantics)
   BHF_HASH_SHA3_256 = 8u,  // msg is a message: digest = SHA3-256(msg) (SHA3 hash family)
+  // internal (outside the public BH_F_* set; bh_verify_bdls_prehashed_dev sets
+  // it in BdlsIn::flags): msg is SignedProto.Hash() itself, not hashed
+  BHF_BDLS_PREHASHED = 0x100u,
 };
 
 // Digest source of a verify record (compile-time, one k_prep instantiation each).
@@ -380,11 +383,38 @@ BH_HD void setbytes_u256(const uint8_t* b, uint32_t len, uint32_t v[8], bool* bi
   }
 }
 
+// BHF_BDLS_PREHASHED records: msg[msg_off, +msg_len) is SignedProto.Hash()
+// itself. e = hashToInt / hashToNat of it for a 256-bit order: the left-most
+// min(len, 32) bytes, big-endian (length 0: e = 0), then one subtraction of n;
+// version is not read. Byte loads: the offsets are arbitrary.
+template <class C>
+BH_HD void stage_bdls_given(const BdlsIn& in, const Work& w, uint32_t i) {
+  uint32_t e[8], nn[8], t[8];
+  const uint8_t* m = in.msg + in.msg_off[i];
+  const uint32_t mlen = in.msg_len[i];
+  const uint32_t L = mlen < 32 ? mlen : 32;
+#pragma unroll
+  for (int k = 0; k < 8; k++) e[k] = 0;
+#pragma unroll
+  for (int j = 0; j < 32; j++) {  // j = byte index from the least significant end
+    uint32_t v = 0;
+    if ((uint32_t)j < L) v = m[L - 1 - j];
+    e[j >> 2] |= v << (8 * (j & 3));
+  }
+  load_const8(nn, C::n);
+  if (!sub8(t, e, nn)) copy8(e, t);  // e < 2^256 < 2n
+  st8(w.e, i, w.ns, e);
+}
+
 // e = SignedProto.Hash() (message.go:97-138) as hashToInt: 32 bytes, then mod n,
 // stored to w.e for stage_prep. One lane per record; the device runs the
 // 4-lanes-per-record k_bdls_hash (verify_kernels.hip) with the same result.
+// This one-lane form is the digest stage of a sequential run: where seq()
+// launches k_bdls_given instead (BHF_BDLS_PREHASHED), it runs that kernel's
+// function.
 template <class C>
 BH_HD void stage_bdls_hash(const BdlsIn& in, const Work& w, uint32_t i) {
+  if (in.flags & BHF_BDLS_PREHASHED) return stage_bdls_given<C>(in, w, i);
   uint8_t hsh[32];
   uint32_t e[8], nn[8], t[8];
   const uint8_t* q = in.xy + (size_t)i * 64;
@@ -398,9 +428,11 @@ BH_HD void stage_bdls_hash(const BdlsIn& in, const Work& w, uint32_t i) {
 // SignedProto.Verify (message.go:170-184): hash = SignedProto.Hash(), then Go
 // crypto/ecdsa.Verify(pub{curve, X, Y}, hash, R, S) with R, S from SetBytes.
 // secp256k1 takes verifyLegacy; P-256 takes verifyNISTEC. No low-S rule.
-// Off-curve / out-of-range keys are rejected (BH_R_BAD_KEY) on both curves:
-// for secp256k1 Go would compute on them, but consensus.go:456-466 admits only
-// registered participants' keys, so such inputs never reach Verify in BDLS.
+// Off-curve / out-of-range keys are rejected on both curves. P-256: as
+// pointFromAffine, first (BH_R_BAD_KEY). secp256k1: verifyLegacy has no key
+// check and would compute on them (consensus.go:456-466 admits only registered
+// participants' keys, so such inputs never reach Verify in BDLS); the record is
+// rejected where Go's group equation would, after the r, s ranges (BH_R_MATH).
 template <class P, class N, class C>
 BH_HD void stage_prep(const BdlsIn& in, const Work& w, uint32_t i) {
   uint8_t reason = R_OK;
@@ -413,9 +445,11 @@ BH_HD void stage_prep(const BdlsIn& in, const Work& w, uint32_t i) {
   if (rzero) reason = R_R_NONPOS;       // ecdsa.Verify: r.Sign() <= 0
   else if (szero) reason = R_S_NONPOS;
   const uint8_t* q = in.xy + (size_t)i * 64;
-  if (reason == R_OK && !key_import<P, C>(q, qx30, qy30)) reason = R_BAD_KEY;
+  const bool badkey = reason == R_OK && !key_import<P, C>(q, qx30, qy30);
+  if (badkey && P::a_is_minus3) reason = R_BAD_KEY;
   if (reason == R_OK && (rbig || geq8(r, nn))) reason = R_R_RANGE;
   if (reason == R_OK && (sbig || geq8(s, nn))) reason = R_S_RANGE;
+  if (reason == R_OK && badkey) reason = R_MATH;
   // e (w.e) is written by stage_bdls_hash / k_bdls_hash, possibly concurrently:
   // prep never touches it (a rejected record's e is any scalar < n)
   uint8_t st = reason;

@@ -62,6 +62,15 @@ __global__ __launch_bounds__(256) void k_digest(BatchIn in, Work w, uint32_t n) 
   st8(w.e, i, w.ns, e);
 }
 
+// BHF_BDLS_PREHASHED batches: e from the caller's SignedProto.Hash() bytes, in
+// k_bdls_hash's place (one lane per record).
+template <class C>
+__global__ __launch_bounds__(256) void k_bdls_given(BdlsIn in, Work w, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  stage_bdls_given<C>(in, w, i);
+}
+
 // Fused SHA-256 digests of a small batch, kDigG lanes per record (round 5).
 // A small batch's digest kernel is a few dozen waves, one per SIMD, each
 // issue-bound on the longest message of its 64 records (a config-3 creator
@@ -128,7 +137,8 @@ __global__ __launch_bounds__(kDigBlock) void k_digest_grp(BatchIn in, Work w, ui
 }
 
 // Fabric records pick the digest source per batch (SHA3 family or not); BDLS
-// records always hash with BLAKE2b.
+// records hash with BLAKE2b (k_bdls_hash) unless the caller supplied the
+// hashes (BHF_BDLS_PREHASHED: k_bdls_given in its place).
 template <class P, class N, class C>
 void launch_prep(const BatchIn& in, const Work& w, uint32_t n, dim3 grd, dim3 blk,
                  hipStream_t s) {
@@ -1359,7 +1369,10 @@ static hipError_t seq(const IN& in, const Work& w, const Plan& pl, const KeyReg&
     joined = false;
   }
   if constexpr (kBdls) {
-    hipLaunchKernelGGL((k_bdls_hash<C>), dim3((n * 4 + 255) / 256), blk, 0, hs, in, w, n);
+    if (in.flags & BHF_BDLS_PREHASHED)
+      hipLaunchKernelGGL((k_bdls_given<C>), grd, blk, 0, hs, in, w, n);
+    else
+      hipLaunchKernelGGL((k_bdls_hash<C>), dim3((n * 4 + 255) / 256), blk, 0, hs, in, w, n);
     if (!joined && (e = hipEventRecord((hipEvent_t)o.ev_join, hs))) return e;
   } else if (split) {
     if (in.flags & BHF_HASH_SHA3_256) {

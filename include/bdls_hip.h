@@ -305,9 +305,11 @@ int bh_parse_der_sig(const uint8_t *der, size_t len, uint8_t r[32], uint8_t s[32
  * curve BH_CURVE_SECP256K1: as wired in orderer/consensus/bdls/chain.go:60-61
  * (Go verifyLegacy); BH_CURVE_P256: the curve-generic BDLS library with P-256
  * keys (verifyNISTEC). No low-S rule. Result reasons: BH_R_OK or a reject
- * code (every reject is Verify() == false). Off-curve keys are rejected with
- * BH_R_BAD_KEY on both curves (BDLS only admits registered participants'
- * keys, consensus.go:456-466). */
+ * code (every reject is Verify() == false). Off-curve / out-of-range keys are
+ * rejected on both curves: BH_R_BAD_KEY on P-256 (pointFromAffine, before the
+ * r, s ranges); on secp256k1, where verifyLegacy has no key check and rejects
+ * such a record in the group equation, BH_R_MATH after the r, s ranges (BDLS
+ * only admits registered participants' keys, consensus.go:456-466). */
 typedef struct bh_bdls_batch {
   const uint8_t *xy;       /* n * 64: SignedProto.X || SignedProto.Y (32 B each)    */
   const uint8_t *r;        /* concatenated SignedProto.R (big-endian, any length)   */
@@ -329,6 +331,16 @@ int bh_verify_bdls(int curve, const bh_bdls_batch *b, size_t n, uint8_t *bitmap,
 int bh_verify_bdls_dev(int device, int curve, const bh_bdls_batch *b, size_t n,
                        uint64_t *bitmap_words, uint8_t *reason, void *stream, int sync,
                        bh_timing *timing);
+/* As bh_verify_bdls_dev for callers that already hold SignedProto.Hash()
+ * (consensus code that caches message hashes): msg[msg_off[i], +msg_len[i]) is
+ * the hash itself and is not hashed again. e is Go's hashToInt / hashToNat of
+ * those bytes for a 256-bit order: the left-most min(len, 32) bytes as a
+ * big-endian integer, minus n once if >= n; length 0 gives e = 0. version is
+ * not read (it may be NULL). Everything after the digest -- checks, reasons,
+ * kernels, streams, timing -- is bh_verify_bdls_dev's. */
+int bh_verify_bdls_prehashed_dev(int device, int curve, const bh_bdls_batch *b, size_t n,
+                                 uint64_t *bitmap_words, uint8_t *reason, void *stream, int sync,
+                                 bh_timing *timing);
 
 /* ---- BDLS drained-batch pre-verification ------------------------------------
  * Replaces the per-message signature work of agent-tcp/tcp_peer.go:176-192
