@@ -10,7 +10,7 @@ LIB  := bdls_amd/lib
 HDRS := $(wildcard $(CSRC)/*.h) include/bdls_hip.h
 
 all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so \
-     tests/native/build/libhostsim384.so $(LIB)/csp_load
+     tests/native/build/libhostsim384.so tests/native/build/libhostsim512.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -18,6 +18,11 @@ $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 
 # the P-384 pass (BH_CURVE_P384): a translation unit of its own
 $(LIB)/verify384_kernels.o: $(CSRC)/verify384_kernels.hip $(HDRS)
+	@mkdir -p $(LIB)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the SHA-384 / SHA-512 digest pre-pass (BH_F_HASH_SHA384 / _SHA512): its own unit too
+$(LIB)/sha512_kernels.o: $(CSRC)/sha512_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -33,7 +38,8 @@ $(LIB)/fabric.o: $(CSRC)/fabric.cpp $(HDRS)
 	@mkdir -p $(LIB)
 	g++ -O2 -std=c++17 -fPIC -Wall -Wno-unknown-pragmas -c $< -o $@
 
-$(LIB)/libbdlship.so: $(LIB)/verify_kernels.o $(LIB)/verify384_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o
+$(LIB)/libbdlship.so: $(LIB)/verify_kernels.o $(LIB)/verify384_kernels.o $(LIB)/sha512_kernels.o \
+                     $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 $(LIB)/libbdlsgen.so: bdls_amd/workload/gen.c
@@ -54,6 +60,16 @@ tests/native/build/libhostsim384.so: tests/native/hostsim384.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
 
+tests/native/build/libhostsim512.so: tests/native_sha512/hostsim_sha512.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
+
+# stand-alone sanitizer run of sha512.h on the CPU (tests/test_sha2wide_cpu.py builds and runs it)
+tests/native/build/sha512_selftest: tests/native_sha512/sha512_selftest.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -o $@ $< -lcrypto
+
 # build-kernel experiments (profiles/r02/exp_build): not part of `all`
 EXP_VARIANTS := base:
 exp:
@@ -61,7 +77,8 @@ exp:
 	@for v in $(EXP_VARIANTS); do n=$${v%%:*}; f=$$(echo $${v#*:} | tr '+' ' '); \
 	  $(HIPCC) $(HIPFLAGS) $$f -c $(CSRC)/verify_kernels.hip -o build/exp/vk_$$n.o && \
 	  $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libbdlship_$$n.so build/exp/vk_$$n.o \
-	    $(LIB)/verify384_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o -lpthread || exit 1; done
+	    $(LIB)/verify384_kernels.o $(LIB)/sha512_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o \
+	    $(LIB)/fabric.o -lpthread || exit 1; done
 
 clean:
 	rm -rf $(LIB) tests/native/build

@@ -19,6 +19,8 @@ BH_F_NO_LOW_S = 2
 BH_F_KEEP_KEYS = 4
 BH_F_HASH_SHA3_256 = 8
 BH_F_ANY_LANE = 16
+BH_F_HASH_SHA384 = 32
+BH_F_HASH_SHA512 = 64
 BH_CURVE_P256 = 0
 BH_CURVE_SECP256K1 = 1
 BH_CURVE_P384 = 2
@@ -37,7 +39,7 @@ EXPORTS = (
     "bh_block_signatures_preverify_bft", "bh_fabric_block_preverify_refs", "bh_device_stats",
     "bh_verify_compact", "bh_verify_compact_submit",
     "bh_batch_verify", "bh_batch_verify_submit", "bh_batch_verify_ptrs",
-    "bh_batch_verify_ptrs_submit", "bh_pack_stats", "bh_curve_key_bytes",
+    "bh_batch_verify_ptrs_submit", "bh_pack_stats", "bh_curve_key_bytes", "bh_verify_x509_ex",
 )
 KEY_FULL = 255  # bh_keys_register status: registry full
 
@@ -228,6 +230,8 @@ def lib() -> ctypes.CDLL:
         L.bh_block_signatures_preverify_bft.restype = i32
         L.bh_verify_x509.argtypes = [vp, vp, vp, vp, sz, vp, vp]
         L.bh_verify_x509.restype = i32
+        L.bh_verify_x509_ex.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp]
+        L.bh_verify_x509_ex.restype = i32
         L.bh_csp_stats.argtypes = [vp]
         L.bh_csp_stats.restype = i32
         try:  # (an A/B run may load a library built before this entry point)

@@ -25,7 +25,8 @@ from typing import Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import BH_F_HASH_SHA256, BH_F_HASH_SHA3_256, BH_F_NO_LOW_S, BhBatch
+from ._lib import (BH_F_HASH_SHA256, BH_F_HASH_SHA3_256, BH_F_HASH_SHA384, BH_F_HASH_SHA512,
+                   BH_F_NO_LOW_S, BhBatch)
 
 # reason codes (include/bdls_hip.h)
 R_OK, R_EMPTY_SIG, R_EMPTY_DIGEST, R_DER, R_R_NONPOS, R_S_NONPOS, R_HIGH_S = range(7)
@@ -103,14 +104,27 @@ class SHA3_256Opts:
     """bccsp/hashopts.go SHA3_256Opts."""
 
 
+class SHA384Opts:
+    """bccsp/hashopts.go SHA384Opts (the sw provider's hash at security level 384)."""
+
+
 # msp/identities.go:219-227 getHashOpt: MSP SignatureHashFamily -> device hash flag
 _FAMILY_FLAG = {"SHA2": BH_F_HASH_SHA256, "SHA3": BH_F_HASH_SHA3_256}
+# batch_identity_verify(hash=...): a hash named outright instead of the MSP's family
+_HASH_FLAG = {"SHA256": BH_F_HASH_SHA256, "SHA3_256": BH_F_HASH_SHA3_256,
+              "SHA384": BH_F_HASH_SHA384, "SHA512": BH_F_HASH_SHA512}
 
 
 def family_flag(family: str) -> int:
     if family not in _FAMILY_FLAG:
         raise BCCSPError(-1, f"hash family not recognized [{family}]")
     return _FAMILY_FLAG[family]
+
+
+def hash_flag(name: str) -> int:
+    if name not in _HASH_FLAG:
+        raise BCCSPError(-1, f"hash function not recognized [{name}]")
+    return _HASH_FLAG[name]
 
 
 def _arr(a: np.ndarray) -> int:
@@ -173,6 +187,8 @@ class HipCSP:
     def hash(self, msg: bytes, opts=None) -> bytes:
         if isinstance(opts, SHA3_256Opts):
             return hashlib.sha3_256(msg).digest()
+        if isinstance(opts, SHA384Opts):
+            return hashlib.sha384(msg).digest()
         return hashlib.sha256(msg).digest()
 
     def key_import(self, raw, opts) -> ECDSAPublicKey:
@@ -216,21 +232,60 @@ class HipCSP:
                              curve=batch_curve(keys))
 
     def batch_identity_verify(self, keys: Sequence[ECDSAPublicKey], messages: Sequence[bytes],
-                              signatures: Sequence[bytes], family: str = "SHA2"):
+                              signatures: Sequence[bytes], family: str = "SHA2",
+                              hash: str | None = None):
         """msp/identities.go:170-199 for a whole batch with the MSP's hash family
-        (SHA2 -> SHA-256, SHA3 -> SHA3-256) fused on device."""
+        (SHA2 -> SHA-256, SHA3 -> SHA3-256) fused on device. hash ("SHA256",
+        "SHA3_256", "SHA384", "SHA512") names the hash outright and overrides
+        family: "SHA384" is the sw provider's level-384 pairing with P-384 keys
+        (bccsp/sw/conf.go:43-46); SHA-384 and SHA-512 run as a digest pass ahead
+        of the curve's pass."""
+        flag = hash_flag(hash) if hash is not None else family_flag(family)
         return verify_packed(*pack_records(keys, signatures, messages),
-                             flags=self._flags | family_flag(family), curve=batch_curve(keys))
+                             flags=self._flags | flag, curve=batch_curve(keys))
 
-    def identity_verify(self, k, msg: bytes, sig: bytes, family: str = "SHA2") -> None:
+    def identity_verify(self, k, msg: bytes, sig: bytes, family: str = "SHA2",
+                        hash: str | None = None) -> None:
         """identity.Verify: raises on error or invalid signature (returns None if valid)."""
-        valid, reason = self.batch_identity_verify([k], [msg], [sig], family)
+        valid, reason = self.batch_identity_verify([k], [msg], [sig], family, hash)
         r = int(reason[0])
         if r in ERROR_REASONS:
             raise BCCSPError(r, "could not determine the validity of the signature: " +
                              _err_text(r, k.curve).replace("%s", "<nil>", 1).replace("%s", "", 1))
         if not valid[0]:
             raise BCCSPError(r, "The signature is invalid")
+
+
+def x509_check_signatures(certs: Sequence[bytes], issuer_keys: Sequence[ECDSAPublicKey]):
+    """bh_verify_x509_ex: certificate i's signature against issuer key i, Go's
+    Certificate.CheckSignatureFrom for ECDSA issuers on P-256 or P-384 with
+    ecdsa-with-SHA256 / -SHA384 / -SHA512 (a chain link of msp/mspimpl.go:717-722).
+    Returns (valid bool[n], reason u8[n]); reason 11 (BH_R_UNSUPPORTED) leaves
+    the certificate to Go's x509."""
+    _lib.ensure_init()
+    n = len(certs)
+    if len(issuer_keys) != n:
+        raise BCCSPError(-1, "one issuer key per certificate")
+    for k in issuer_keys:
+        if k.curve not in _CURVES:
+            raise BCCSPError(-1, f"Unsupported 'VerifyKey' curve [{k.curve}]")
+    raws = [k.raw() for k in issuer_keys]
+    pub = np.frombuffer(b"".join(raws) + b"\0", dtype=np.uint8)
+    curve = np.array([_CURVES[k.curve][0] for k in issuer_keys], dtype=np.uint8)
+    pub_len = np.fromiter((len(r) for r in raws), dtype=np.uint64, count=n)
+    cert_len = np.fromiter((len(c) for c in certs), dtype=np.uint32, count=n)
+    pub_off = np.zeros(n, dtype=np.uint64)
+    cert_off = np.zeros(n, dtype=np.uint64)
+    if n:
+        pub_off[1:] = np.cumsum(pub_len[:-1], dtype=np.uint64)
+        cert_off[1:] = np.cumsum(cert_len[:-1], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(certs) + b"\0", dtype=np.uint8)
+    bitmap = np.zeros((n + 7) // 8 or 1, dtype=np.uint8)
+    reason = np.zeros(n or 1, dtype=np.uint8)
+    _lib.check(_lib.lib().bh_verify_x509_ex(buf.ctypes.data, _arr(cert_off), _arr(cert_len),
+                                            pub.ctypes.data, _arr(pub_off), _arr(curve), n,
+                                            bitmap.ctypes.data, reason.ctypes.data))
+    return np.unpackbits(bitmap, bitorder="little")[:n].astype(bool), reason[:n]
 
 
 def parse_der_sig(der: bytes):

@@ -47,6 +47,9 @@ hipError_t launch_small(int curve, const BatchIn& in, const Work& w, const KeyRe
 hipError_t launch_register(int curve, const uint8_t* pub, const Work& w, const Plan& pl,
                            const KeyReg& g, uint32_t n, uint8_t* status, hipStream_t s);
 hipError_t launch_gtab384_build(uint32_t* gtab, hipStream_t s);
+hipError_t launch_sha512(int out_bytes, const uint8_t* msg, const uint64_t* msg_off,
+                         const uint32_t* msg_len, uint32_t n, uint8_t* dig, uint64_t* off,
+                         uint32_t* len, hipStream_t s);
 hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* gtab, uint32_t n,
                             uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev);
 size_t expand_temp_bytes(uint32_t m);
@@ -222,6 +225,9 @@ struct Dev {
   DevBuf ws384;                 // Work384
   DevBuf in384, out384;         // bh_verify: one chunk's inputs / bitmap words + reasons
   hipEvent_t ev384[4] = {nullptr, nullptr, nullptr, nullptr};
+  // BH_F_HASH_SHA384 / BH_F_HASH_SHA512 (allocated at the device's first such call, under mu)
+  DevBuf dig512;  // one chunk's digests, offsets and lengths: the curve pass's digest batch
+  hipEvent_t ev512[2] = {nullptr, nullptr};
   DevBuf ws;     // Work + Plan
   DevBuf stage;  // key registration input
   DevBuf out;    // key registration status
@@ -489,6 +495,11 @@ void dev_free(Dev& d) {
   d.ws384.release();
   d.in384.release();
   d.out384.release();
+  d.dig512.release();
+  for (auto& e : d.ev512) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
   for (auto& e : d.ev384) {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
@@ -622,7 +633,7 @@ hipError_t launch(int curve, const bh::BdlsIn& in, const bh::Work& w, const bh::
 template <class B>
 int run_dev(Dev& d, int curve, const B* b, size_t n, uint32_t flags, uint64_t* bitmap,
             uint8_t* reason, hipStream_t s, bh_timing* t, int lane = -1,
-            hipEvent_t records_ready = nullptr) {
+            hipEvent_t records_ready = nullptr, bool count = true) {
   if (t) *t = bh_timing{};
   if (flags & BH_F_KEEP_KEYS) lane = -1;
   if ((flags & BH_F_KEEP_KEYS) && d.reg[curve].g.cap == 0) {
@@ -630,8 +641,10 @@ int run_dev(Dev& d, int curve, const B* b, size_t n, uint32_t flags, uint64_t* b
     if (rc) return rc;
   }
   const LaneRef L = lane_ref(d, lane);  // lane < 0: lane 0's resources, after every lane
-  g_dev_batches.fetch_add(1, std::memory_order_relaxed);
-  g_dev_records.fetch_add(n, std::memory_order_relaxed);
+  if (count) {  // (not the chunks of a call that counted itself)
+    g_dev_batches.fetch_add(1, std::memory_order_relaxed);
+    g_dev_records.fetch_add(n, std::memory_order_relaxed);
+  }
   if (lane < 0) {
     HIPCHK(wait_lanes(d, s));
   } else {
@@ -1694,12 +1707,23 @@ int check_curve(int curve) {
   return BH_OK;
 }
 
-int check_flags(uint32_t flags) {
-  constexpr uint32_t known =
-      BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_KEEP_KEYS | BH_F_HASH_SHA3_256 | BH_F_ANY_LANE;
+constexpr uint32_t kWideHash = BH_F_HASH_SHA384 | BH_F_HASH_SHA512;
+
+// fn: the entry point when it does not take BH_F_HASH_SHA384 / BH_F_HASH_SHA512
+// (nullptr: bh_verify and bh_verify_dev, which do).
+int check_flags(uint32_t flags, const char* fn = nullptr) {
+  constexpr uint32_t known = BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_KEEP_KEYS |
+                             BH_F_HASH_SHA3_256 | BH_F_ANY_LANE | kWideHash;
   if (flags & ~known) return fail(BH_E_INVALID, "unknown flag");
   if ((flags & BH_F_HASH_SHA256) && (flags & BH_F_HASH_SHA3_256))
     return fail(BH_E_INVALID, "BH_F_HASH_SHA256 and BH_F_HASH_SHA3_256 are exclusive");
+  const uint32_t hashes = flags & (BH_F_HASH_SHA256 | BH_F_HASH_SHA3_256 | kWideHash);
+  if (hashes & (hashes - 1))
+    return fail(BH_E_INVALID, "the BH_F_HASH_* flags are mutually exclusive");
+  if (fn && (flags & kWideHash))
+    return fail(BH_E_INVALID, std::string((flags & BH_F_HASH_SHA384) ? "BH_F_HASH_SHA384"
+                                                                       : "BH_F_HASH_SHA512") +
+                                  " not supported by " + fn + ": use bh_verify or bh_verify_dev");
   return BH_OK;
 }
 
@@ -1798,10 +1822,76 @@ int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bi
   return BH_OK;
 }
 
-// bh_verify for BH_CURVE_P384: the first initialised device alone; upload, run
-// and download chunk by chunk, synchronously.
-int host_verify384(const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+// ---- BH_F_HASH_SHA384 / BH_F_HASH_SHA512 ---------------------------------------
+// A device-resident batch of either NIST curve whose messages hash with the
+// SHA-512 family, on stream s: per chunk (P-384: BH_P384_CHUNK records), the digest
+// pass (k_sha512: every record, also those the curve pass rejects before it
+// needs a digest) into the device's digest buffer, then the curve's pass in
+// digest mode over that buffer -- hashToNat takes the leftmost 32 (P-256) or
+// 48 (P-384) bytes. Behind every lane's work, like run_dev384: the buffer is
+// one per device. Caller holds d.mu, device set, and counts the batch.
+int run_dev_wide(Dev& d, int curve, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bitmap,
+                 uint8_t* reason, hipStream_t s, bh_timing* t) {
+  if (t) *t = bh_timing{};
+  const int ob = (flags & BH_F_HASH_SHA384) ? 48 : 64;
+  const size_t kb = curve == BH_CURVE_P384 ? 96 : 64;
+  const uint32_t rest = flags & BH_F_NO_LOW_S;  // BH_F_KEEP_KEYS / BH_F_ANY_LANE: ignored
+  // P-256: one digest pass ahead of the whole batch (run_dev splits by its own
+  // bound): its pass builds key tables per pass, so passes of BH_P384_CHUNK
+  // records would build the tables of the same keys again and again
+  const size_t chunk = curve == BH_CURVE_P384 ? p384_chunk() : kMaxChunk;
+  if (t) {
+    for (auto& ev : d.ev512)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+  }
+  for (size_t base = 0; base < n; base += chunk) {
+    const size_t m = std::min(chunk, n - base);
+    // the digest buffer is reused (and may be reallocated): the pass that read it is done
+    if (int rc = sync_lanes(d)) return rc;
+    const size_t need = round256(m * ob) + round256(m * 8) + round256(m * 4);
+    if (need > d.dig512.cap) HIPCHK(hipDeviceSynchronize());
+    if (int rc = d.dig512.ensure(need)) return rc;
+    uint8_t* dig = (uint8_t*)d.dig512.p;
+    uint64_t* off = (uint64_t*)(dig + round256(m * ob));
+    uint32_t* len = (uint32_t*)((uint8_t*)off + round256(m * 8));
+    HIPCHK(wait_lanes(d, s));
+    if (t) HIPCHK(hipEventRecord(d.ev512[0], s));
+    HIPCHK(bh::launch_sha512(ob, b->msg, b->msg_off + base, b->msg_len + base, (uint32_t)m, dig,
+                             off, len, s));
+    if (t) HIPCHK(hipEventRecord(d.ev512[1], s));
+    const bh_batch db{b->pub + base * kb, b->sig, b->sig_off + base, b->sig_len + base,
+                      dig,                off,    len};
+    bh_timing tc{};
+    const int rc = curve == BH_CURVE_P384
+                       ? run_dev384(d, &db, m, rest, bitmap + base / 64, reason + base, s,
+                                    t ? &tc : nullptr)
+                       : run_dev(d, curve, &db, m, rest, bitmap + base / 64, reason + base, s,
+                                 t ? &tc : nullptr, -1, nullptr, false);
+    if (rc) return rc;
+    if (t) {  // (the curve pass has synchronised)
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, d.ev512[0], d.ev512[1]));
+      t->prep_ms += ms + tc.prep_ms;
+      t->inv_ms += tc.inv_ms;
+      t->plan_ms += tc.plan_ms;
+      t->build_ladder_ms += tc.build_ladder_ms;
+      t->publish_ms += tc.publish_ms;
+      t->keycomb_ms += tc.keycomb_ms;
+      t->n_keycomb += tc.n_keycomb;
+      t->n_ladder += tc.n_ladder;
+      t->n_keytables += tc.n_keytables;
+      t->wide = tc.wide;
+    }
+  }
+  return BH_OK;
+}
+
+// bh_verify for BH_CURVE_P384, and for either curve with BH_F_HASH_SHA384 /
+// BH_F_HASH_SHA512: the first initialised device alone; upload, run and
+// download chunk by chunk, synchronously.
+int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
                    uint8_t* reason) {
+  const size_t kb = curve == BH_CURVE_P384 ? 96 : 64;
   std::vector<Dev*> ds = all_devs();
   if (ds.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
   Dev& d = *ds[0];
@@ -1836,7 +1926,7 @@ int host_verify384(const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
     if ((sbytes && !b->sig) || (mbytes && !b->msg)) return fail(BH_E_INVALID, "null pointer in batch");
     if (int rc = sync_lanes(d)) return rc;
     HIPCHK(hipStreamSynchronize(s));  // the staging below is reused chunk after chunk
-    const size_t total = round256(m * 96) + 2 * round256(m * 8) + 2 * round256(m * 4) +
+    const size_t total = round256(m * kb) + 2 * round256(m * 8) + 2 * round256(m * 4) +
                          round256(sbytes + 8) + round256(mbytes + 8);
     if (int rc = d.in384.ensure(total)) return rc;
     if (int rc = d.out384.ensure(round256(round64(m) / 8) + round256(m))) return rc;
@@ -1849,25 +1939,27 @@ int host_verify384(const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
     };
     bh_batch db;
     char* q;
-    if (!(q = put(b->pub + base * 96, m * 96, m * 96))) return fail(BH_E_DEVICE, "P-384 upload");
+    if (!(q = put(b->pub + base * kb, m * kb, m * kb))) return fail(BH_E_DEVICE, "chunk upload");
     db.pub = (const uint8_t*)q;
-    if (!(q = put(so.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "P-384 upload");
+    if (!(q = put(so.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "chunk upload");
     db.sig_off = (const uint64_t*)q;
-    if (!(q = put(mo.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "P-384 upload");
+    if (!(q = put(mo.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "chunk upload");
     db.msg_off = (const uint64_t*)q;
-    if (!(q = put(b->sig_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "P-384 upload");
+    if (!(q = put(b->sig_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "chunk upload");
     db.sig_len = (const uint32_t*)q;
-    if (!(q = put(b->msg_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "P-384 upload");
+    if (!(q = put(b->msg_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "chunk upload");
     db.msg_len = (const uint32_t*)q;
     if (!(q = put(sbytes ? b->sig + slo : nullptr, sbytes, sbytes + 8)))
-      return fail(BH_E_DEVICE, "P-384 upload");
+      return fail(BH_E_DEVICE, "chunk upload");
     db.sig = (const uint8_t*)q;
     if (!(q = put(mbytes ? b->msg + mlo : nullptr, mbytes, mbytes + 8)))
-      return fail(BH_E_DEVICE, "P-384 upload");
+      return fail(BH_E_DEVICE, "chunk upload");
     db.msg = (const uint8_t*)q;
     uint64_t* dbm = (uint64_t*)d.out384.p;
     uint8_t* drs = (uint8_t*)d.out384.p + round256(round64(m) / 8);
-    if (int rc = run_dev384(d, &db, m, flags, dbm, drs, s, nullptr)) return rc;
+    if (int rc = (flags & kWideHash) ? run_dev_wide(d, curve, &db, m, flags, dbm, drs, s, nullptr)
+                                     : run_dev384(d, &db, m, flags, dbm, drs, s, nullptr))
+      return rc;
     words.resize(round64(m) / 64);
     HIPCHK(hipMemcpyAsync(words.data(), dbm, words.size() * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(reason + base, drs, m, hipMemcpyDeviceToHost, s));
@@ -2325,13 +2417,17 @@ int bh_verify_dev(int device, int curve, const bh_batch* b, size_t n, uint32_t f
   if (!d) return fail(BH_E_NOT_INIT, "device not initialised (call bh_init)");
   std::lock_guard<std::mutex> g(d->mu);
   HIPCHK(hipSetDevice(d->id));
-  if (curve == BH_CURVE_P384) {  // BH_F_KEEP_KEYS / BH_F_ANY_LANE: ignored for this curve
+  // BH_F_KEEP_KEYS / BH_F_ANY_LANE: ignored for this curve and these hashes
+  if (curve == BH_CURVE_P384 || (flags & kWideHash)) {
     hipStream_t s384 = stream ? (hipStream_t)stream : d->stream;
     if (timing) *timing = bh_timing{};
     if (n == 0) return BH_OK;
     g_dev_batches.fetch_add(1, std::memory_order_relaxed);
     g_dev_records.fetch_add(n, std::memory_order_relaxed);
-    if (int rc = run_dev384(*d, b, n, flags, bitmap_words, reason, s384, timing)) return rc;
+    if (int rc = (flags & kWideHash)
+                     ? run_dev_wide(*d, curve, b, n, flags, bitmap_words, reason, s384, timing)
+                     : run_dev384(*d, b, n, flags, bitmap_words, reason, s384, timing))
+      return rc;
     if (sync && !timing) HIPCHK(hipStreamSynchronize(s384));
     return BH_OK;
   }
@@ -2364,7 +2460,8 @@ int bh_verify(int curve, const bh_batch* b, size_t n, uint32_t flags, uint8_t* b
     return curve_unsupported(curve, "bh_verify");
   if (int rc = check_flags(flags)) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
-  if (curve == BH_CURVE_P384) return host_verify384(b, n, flags, bitmap, reason);
+  if (curve == BH_CURVE_P384 || (flags & kWideHash))
+    return host_verify_chunked(curve, b, n, flags, bitmap, reason);
   return host_verify(curve, b, n, flags, bitmap, reason);
 }
 
@@ -2375,7 +2472,7 @@ int bh_verify_2seg(int curve, const bh_batch* b, const uint64_t* msg2_off,
                    !msg2_off || !msg2_len || !bitmap || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
   if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_2seg");
-  if (int rc = check_flags(flags)) return rc;
+  if (int rc = check_flags(flags, "bh_verify_2seg")) return rc;
   if (!(flags & (BH_F_HASH_SHA256 | BH_F_HASH_SHA3_256)))
     return fail(BH_E_INVALID, "bh_verify_2seg hashes on the device: pass BH_F_HASH_SHA256 or "
                               "BH_F_HASH_SHA3_256");
@@ -2392,7 +2489,7 @@ int bh_verify_submit(int curve, const bh_batch* b, size_t n, uint32_t flags, uin
                    !bitmap || !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
   if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_submit");
-  if (int rc = check_flags(flags)) return rc;
+  if (int rc = check_flags(flags, "bh_verify_submit")) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   return submit_job(curve, b, n, flags, bitmap, reason, job);
 }
@@ -2416,7 +2513,7 @@ static int check_compact(const bh_cbatch* b, size_t n, const uint8_t* bitmap,
 int bh_verify_compact(int curve, const bh_cbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
                       uint8_t* reason) {
   if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_compact");
-  if (int rc = check_flags(flags)) return rc;
+  if (int rc = check_flags(flags, "bh_verify_compact")) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   if (int rc = check_compact(b, n, bitmap, reason)) return rc;
   const CompactHost h{*b};
@@ -2428,7 +2525,7 @@ int bh_verify_compact_submit(int curve, const bh_cbatch* b, size_t n, uint32_t f
   if (!job) return fail(BH_E_INVALID, "null job");
   *job = nullptr;
   if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_verify_compact_submit");
-  if (int rc = check_flags(flags)) return rc;
+  if (int rc = check_flags(flags, "bh_verify_compact_submit")) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   if (int rc = check_compact(b, n, bitmap, reason)) return rc;
   const CompactHost h{*b};
@@ -2438,7 +2535,7 @@ int bh_verify_compact_submit(int curve, const bh_cbatch* b, size_t n, uint32_t f
 // ---- staged BatchVerify (pack.h) ----
 static int check_staged(int curve, uint32_t flags, size_t n) {
   if (curve != BH_CURVE_P256) return curve_unsupported(curve, "bh_batch_verify");
-  if (int rc = check_flags(flags)) return rc;
+  if (int rc = check_flags(flags, "bh_batch_verify and bh_batch_verify_ptrs")) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
   return BH_OK;
 }

@@ -516,6 +516,8 @@ bool tlv(const uint8_t* b, size_t n, size_t* off, Tlv* t) {
 const uint8_t kOidEcPub[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x02, 0x01};
 const uint8_t kOidP256[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x03, 0x01, 0x07};
 const uint8_t kOidEcdsaSha256[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x04, 0x03, 0x02};
+const uint8_t kOidEcdsaSha384[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x04, 0x03, 0x03};
+const uint8_t kOidEcdsaSha512[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x04, 0x03, 0x04};
 
 struct Cert {
   Tlv tbs;               // tbsCertificate (raw = the signed bytes)
@@ -1239,8 +1241,9 @@ void der_uint(std::vector<uint8_t>* o, const std::vector<uint8_t>& v) {
 }
 
 // canonical DER of (r, s): what the device's Go-asn1 parser reads back
-// exactly (an r or s above 32 significant bytes parses as out of range there,
-// as bigmod's SetBytes rejects it in Go)
+// exactly (an r or s with more significant bytes than the curve's order -- 32
+// for P-256, 48 for P-384 -- parses as out of range there, as bigmod's
+// SetBytes rejects it in Go)
 void canon_sig(std::vector<uint8_t>* o, const std::vector<uint8_t>& r,
                const std::vector<uint8_t>& s) {
   std::vector<uint8_t> body;
@@ -1249,6 +1252,37 @@ void canon_sig(std::vector<uint8_t>* o, const std::vector<uint8_t>& r,
   o->push_back(0x30);
   der_len(o, body.size());
   o->insert(o->end(), body.begin(), body.end());
+}
+
+// Certificate ::= SEQUENCE { tbsCertificate, signatureAlgorithm,
+// signatureValue BIT STRING }; the algorithm OIDs of the outer field and
+// of the TBS signature field must match (x509.ParseCertificate). False: not
+// a certificate this walk handles.
+bool x509_parts(const uint8_t* d, size_t dn, Tlv* tbs, Tlv* sv, Tlv* outer_oid) {
+  size_t off = 0, o = 0;
+  Tlv cert, alg;
+  if (!tlv(d, dn, &off, &cert) || cert.tag != 0x30 || off != dn) return false;
+  if (!tlv(cert.p, cert.n, &o, tbs) || tbs->tag != 0x30) return false;
+  if (!tlv(cert.p, cert.n, &o, &alg) || alg.tag != 0x30) return false;
+  if (!tlv(cert.p, cert.n, &o, sv) || sv->tag != 0x03 || sv->n < 1 || sv->p[0] != 0) return false;
+  size_t ao = 0;
+  if (!tlv(alg.p, alg.n, &ao, outer_oid) || outer_oid->tag != 0x06) return false;
+  size_t t = 0;
+  Tlv f;
+  if (!tlv(tbs->p, tbs->n, &t, &f)) return false;
+  if (f.tag == 0xa0 && !tlv(tbs->p, tbs->n, &t, &f)) return false;
+  if (f.tag != 0x02) return false;
+  Tlv inner, inner_oid;
+  if (!tlv(tbs->p, tbs->n, &t, &inner) || inner.tag != 0x30) return false;
+  size_t io = 0;
+  if (!tlv(inner.p, inner.n, &io, &inner_oid) || inner_oid.raw_n != outer_oid->raw_n ||
+      memcmp(inner_oid.raw, outer_oid->raw, inner_oid.raw_n))
+    return false;
+  return true;
+}
+
+bool oid_is(const Tlv& oid, const uint8_t (&want)[8]) {
+  return oid.n == sizeof(want) && !memcmp(oid.p, want, sizeof(want));
 }
 
 }  // namespace
@@ -1273,31 +1307,10 @@ extern "C" int bh_verify_x509(const uint8_t* certs, const uint64_t* cert_off,
     reason[i] = BH_R_UNSUPPORTED;
     const uint8_t* d = certs + cert_off[i];
     const size_t dn = cert_len[i];
-    // Certificate ::= SEQUENCE { tbsCertificate, signatureAlgorithm,
-    // signatureValue BIT STRING }; the algorithm OIDs of the outer field and
-    // of the TBS signature field must match (x509.ParseCertificate)
-    size_t off = 0, o = 0;
-    Tlv cert, tbs, alg, sv, outer_oid;
-    if (!tlv(d, dn, &off, &cert) || cert.tag != 0x30 || off != dn) continue;
-    if (!tlv(cert.p, cert.n, &o, &tbs) || tbs.tag != 0x30) continue;
-    if (!tlv(cert.p, cert.n, &o, &alg) || alg.tag != 0x30) continue;
-    if (!tlv(cert.p, cert.n, &o, &sv) || sv.tag != 0x03 || sv.n < 1 || sv.p[0] != 0) continue;
-    size_t ao = 0;
-    if (!tlv(alg.p, alg.n, &ao, &outer_oid) || outer_oid.tag != 0x06) continue;
-    size_t t = 0;
-    Tlv f;
-    if (!tlv(tbs.p, tbs.n, &t, &f)) continue;
-    if (f.tag == 0xa0 && !tlv(tbs.p, tbs.n, &t, &f)) continue;
-    if (f.tag != 0x02) continue;
-    Tlv inner, inner_oid;
-    if (!tlv(tbs.p, tbs.n, &t, &inner) || inner.tag != 0x30) continue;
-    size_t io = 0;
-    if (!tlv(inner.p, inner.n, &io, &inner_oid) || inner_oid.raw_n != outer_oid.raw_n ||
-        memcmp(inner_oid.raw, outer_oid.raw, inner_oid.raw_n))
-      continue;
-    if (outer_oid.n != sizeof(kOidEcdsaSha256) ||
-        memcmp(outer_oid.p, kOidEcdsaSha256, sizeof(kOidEcdsaSha256)))
-      continue;  // SHA-384 / SHA-512 / RSA: Go's x509 path
+    Tlv tbs, sv, outer_oid;
+    if (!x509_parts(d, dn, &tbs, &sv, &outer_oid)) continue;
+    if (!oid_is(outer_oid, kOidEcdsaSha256))
+      continue;  // SHA-384 / SHA-512: bh_verify_x509_ex; RSA: Go's x509 path
     Cert c;
     c.tbs = tbs;
     c.sig = Tlv{0x03, sv.p + 1, sv.n - 1, sv.raw, sv.raw_n};
@@ -1327,6 +1340,78 @@ extern "C" int bh_verify_x509(const uint8_t* certs, const uint64_t* cert_off,
     const size_t i = which[k];
     reason[i] = rs[k];
     if (rs[k] == BH_R_OK) bitmap[i >> 3] |= (uint8_t)(1u << (i & 7));
+  }
+  return BH_OK;
+}
+
+// bh_verify_x509 with the issuer's curve per record and the three SHA-2
+// algorithms: checkSignature takes the hash from the certificate's algorithm
+// and the curve from the parent's key. Records are grouped by (curve, hash);
+// each group is one bh_verify with that curve and BH_F_HASH_* flag.
+extern "C" int bh_verify_x509_ex(const uint8_t* certs, const uint64_t* cert_off,
+                                 const uint32_t* cert_len, const uint8_t* issuer_pub,
+                                 const uint64_t* issuer_pub_off, const uint8_t* issuer_curve,
+                                 size_t n, uint8_t* bitmap, uint8_t* reason) {
+  if (n && (!certs || !cert_off || !cert_len || !issuer_pub || !issuer_pub_off || !issuer_curve ||
+            !bitmap || !reason))
+    return bh::host_fail(BH_E_INVALID, "null argument");
+  if (n > 0xffffffffull) return bh::host_fail(BH_E_INVALID, "batch too large");
+  for (size_t i = 0; i < n; i++)
+    if (issuer_curve[i] != BH_CURVE_P256 && issuer_curve[i] != BH_CURVE_P384)
+      return bh::host_fail(BH_E_INVALID,
+                           "bh_verify_x509_ex: issuer_curve must be BH_CURVE_P256 or BH_CURVE_P384");
+  memset(bitmap, 0, (n + 7) / 8);
+  struct Group {
+    int curve;
+    uint32_t hash;
+    std::vector<uint8_t> pub, sigs;
+    std::vector<size_t> which;
+    std::vector<uint64_t> tbs_off, sig_off;
+    std::vector<uint32_t> tbs_len, sig_len;
+  };
+  Group groups[6];
+  for (int g = 0; g < 6; g++) {
+    groups[g].curve = g < 3 ? BH_CURVE_P256 : BH_CURVE_P384;
+    groups[g].hash = g % 3 == 0 ? BH_F_HASH_SHA256 : g % 3 == 1 ? BH_F_HASH_SHA384 : BH_F_HASH_SHA512;
+  }
+  for (size_t i = 0; i < n; i++) {
+    reason[i] = BH_R_UNSUPPORTED;
+    const uint8_t* d = certs + cert_off[i];
+    Tlv tbs, sv, oid;
+    if (!x509_parts(d, cert_len[i], &tbs, &sv, &oid)) continue;
+    const int h = oid_is(oid, kOidEcdsaSha256) ? 0 : oid_is(oid, kOidEcdsaSha384) ? 1
+                  : oid_is(oid, kOidEcdsaSha512) ? 2 : -1;
+    if (h < 0) continue;  // SHA-1 / SHA-224 / RSA / EdDSA: Go's x509 path
+    std::vector<uint8_t> r, s;
+    if (!strict_sig(sv.p + 1, sv.n - 1, &r, &s)) {
+      reason[i] = BH_R_DER;  // parseSignature fails: VerifyASN1 false
+      continue;
+    }
+    Group& g = groups[(issuer_curve[i] == BH_CURVE_P384 ? 3 : 0) + h];
+    const size_t kb = g.curve == BH_CURVE_P384 ? 96 : 64;
+    g.pub.insert(g.pub.end(), issuer_pub + issuer_pub_off[i], issuer_pub + issuer_pub_off[i] + kb);
+    g.sig_off.push_back(g.sigs.size());
+    canon_sig(&g.sigs, r, s);
+    g.sig_len.push_back((uint32_t)(g.sigs.size() - g.sig_off.back()));
+    g.tbs_off.push_back(cert_off[i] + (uint64_t)(tbs.raw - d));
+    g.tbs_len.push_back((uint32_t)tbs.raw_n);
+    g.which.push_back(i);
+  }
+  for (Group& g : groups) {
+    const size_t m = g.which.size();
+    if (!m) continue;
+    std::vector<uint8_t> bm((m + 7) / 8), rs(m);
+    g.sigs.push_back(0);
+    // messages: the TBS bytes inside the caller's certificate buffer
+    bh_batch bb{g.pub.data(),     g.sigs.data(),    g.sig_off.data(), g.sig_len.data(), certs,
+                g.tbs_off.data(), g.tbs_len.data()};
+    int rc = bh_verify(g.curve, &bb, m, BH_F_NO_LOW_S | g.hash, bm.data(), rs.data());
+    if (rc) return rc;
+    for (size_t k = 0; k < m; k++) {
+      const size_t i = g.which[k];
+      reason[i] = rs[k];
+      if (rs[k] == BH_R_OK) bitmap[i >> 3] |= (uint8_t)(1u << (i & 7));
+    }
   }
   return BH_OK;
 }

@@ -1,8 +1,9 @@
 """Which kernel build a measurement describes.
 
 `kernel_src_sha()` hashes the sources the HIP code object is compiled from
-(bdls_amd/csrc/verify_kernels.hip, every header under bdls_amd/csrc/, and the
-Makefile that holds the compile flags). build() records it in
+(the kernel units linked into the library -- bdls_amd/csrc/verify_kernels.hip,
+verify384_kernels.hip, sha512_kernels.hip -- every header under bdls_amd/csrc/,
+and the Makefile that holds the compile flags). build() records it in
 bdls_amd/lib/BUILD_INFO.json with the library's sha256, tools/pmc_summary.py
 stamps it into profiles/traffic.json, and bench.py prints PMC counters only
 when the stamp equals the hash the LOADED library was built from
@@ -24,7 +25,9 @@ BUILD_INFO = os.path.join(ROOT, "bdls_amd", "lib", "BUILD_INFO.json")
 def kernel_sources() -> list[str]:
     csrc = os.path.join(ROOT, "bdls_amd", "csrc")
     return sorted(glob.glob(os.path.join(csrc, "*.h"))) + \
-        [os.path.join(csrc, "verify_kernels.hip"), os.path.join(ROOT, "Makefile")]
+        [os.path.join(csrc, f) for f in ("verify_kernels.hip", "verify384_kernels.hip",
+                                         "sha512_kernels.hip")] + \
+        [os.path.join(ROOT, "Makefile")]
 
 
 def kernel_src_sha() -> str:

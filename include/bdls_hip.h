@@ -52,7 +52,8 @@ extern "C" {
 #define BH_R_MATH 9         /* ecdsa.Verify: x(u1 G + u2 Q) mod n != r, or infinity    -> false */
 #define BH_R_S_RANGE 10     /* ecdsa.Verify: s >= n (only with BH_F_NO_LOW_S)           -> false */
 #define BH_R_UNSUPPORTED 11 /* bh_verify_x509: not an ecdsa-with-SHA256 P-256 certificate
-                               signature this engine checks (the caller uses Go's x509)   */
+                               signature this engine checks (the caller uses Go's x509);
+                               bh_verify_x509_ex: not ecdsa-with-SHA256 / -SHA384 / -SHA512 */
 
 /* ---- flags ---- */
 #define BH_F_HASH_SHA256 1u /* msg[i] is a message; digest = SHA-256(msg[i]) (identity.Verify) */
@@ -72,6 +73,29 @@ extern "C" {
                                rotates 4 output sets never has two in-flight passes
                                writing one set; bh_sync waits for every lane.
                                Ignored elsewhere (host batches already alternate lanes). */
+#define BH_F_HASH_SHA384 32u /* msg[i] is a message; digest = SHA-384(msg[i]): the hash of the
+                                sw provider's security level 384 (bccsp/sw/conf.go:43-46,
+                                bccsp/sw/new.go:69-73, SHA384Opts) and of ecdsa-with-SHA384
+                                certificates. */
+#define BH_F_HASH_SHA512 64u /* msg[i] is a message; digest = SHA-512(msg[i]) (ecdsa-with-SHA512
+                                certificates).
+                                Both are taken by bh_verify and bh_verify_dev only, for
+                                BH_CURVE_P256 and BH_CURVE_P384, with the semantics of
+                                BH_F_HASH_SHA256 (length 0 hashes the empty message, an empty
+                                signature is BH_R_EMPTY_SIG, low-S unless BH_F_NO_LOW_S; reasons,
+                                precedence and bitmap unchanged); e = hashToNat of the digest:
+                                its leftmost 32 bytes (P-256) or 48 (P-384), reduced mod n. The
+                                four BH_F_HASH_* flags are mutually exclusive. A digest pass
+                                hashes every record of a chunk into library workspace (not part
+                                of bh_workspace_bytes; allocated per device at first use) and
+                                the curve's pass then runs in digest mode. With either flag,
+                                BH_F_ANY_LANE and BH_F_KEEP_KEYS are ignored, and a P-256
+                                batch runs the way a P-384 batch does: behind every lane's
+                                work, and bh_verify on the first initialised device alone in
+                                chunks of BH_P384_CHUNK records (bh_verify_dev hashes a
+                                resident P-256 batch in one pass). bh_timing.prep_ms includes
+                                the digest pass; bh_device_stats counts one batch per call.
+                                Every other entry point answers BH_E_INVALID for them. */
 
 #define BH_CURVE_P256 0
 #define BH_CURVE_SECP256K1 1
@@ -600,6 +624,24 @@ int bh_block_signatures_preverify_bft(const uint8_t *blocks, const uint64_t *blo
  * or not a certificate this parser walks). */
 int bh_verify_x509(const uint8_t *certs, const uint64_t *cert_off, const uint32_t *cert_len,
                    const uint8_t *issuer_pub, size_t n, uint8_t *bitmap, uint8_t *reason);
+
+/* bh_verify_x509 for issuers on either NIST curve of the sw provider and the
+ * three SHA-2 algorithms crypto/x509 signs ECDSA certificates with (a P-384 CA
+ * key makes x509.CreateCertificate, and fabric-ca with it, choose
+ * ecdsa-with-SHA384). Record i's issuer key is bh_curve_key_bytes(
+ * issuer_curve[i]) bytes at issuer_pub + issuer_pub_off[i]; issuer_curve[i] is
+ * BH_CURVE_P256 or BH_CURVE_P384, anything else BH_E_INVALID for the call.
+ * Accepted, with inner and outer OID equal: ecdsa-with-SHA256
+ * (1.2.840.10045.4.3.2), -SHA384 (4.3.3), -SHA512 (4.3.4); the hash comes from
+ * the algorithm and the curve from the key, independently (checkSignature), so
+ * all six pairings verify: e is the leftmost 32 / 48 bytes of the digest.
+ * Everything else is BH_R_UNSUPPORTED. After the algorithm check the semantics
+ * and reason codes are those of bh_verify_x509, with r, s in [1, n-1] for the
+ * issuer's n. Records are grouped by (curve, hash) and each group runs through
+ * bh_verify with BH_F_NO_LOW_S and the group's BH_F_HASH_* flag. */
+int bh_verify_x509_ex(const uint8_t *certs, const uint64_t *cert_off, const uint32_t *cert_len,
+                      const uint8_t *issuer_pub, const uint64_t *issuer_pub_off,
+                      const uint8_t *issuer_curve, size_t n, uint8_t *bitmap, uint8_t *reason);
 
 /* ---- device buffers on an initialised device (callers that keep batches
  * resident in HBM, e.g. bench.py; the library owns the HIP runtime so callers
