@@ -40,8 +40,9 @@ EXPORTS = (
     "bh_verify_compact", "bh_verify_compact_submit",
     "bh_batch_verify", "bh_batch_verify_submit", "bh_batch_verify_ptrs",
     "bh_batch_verify_ptrs_submit", "bh_pack_stats", "bh_curve_key_bytes", "bh_verify_x509_ex",
+    "bh_keys384_reserve", "bh_keys384_register", "bh_keys384_clear", "bh_keys384_count",
 )
-KEY_FULL = 255  # bh_keys_register status: registry full
+KEY_FULL = 255  # bh_keys_register / bh_keys384_register status: registry full
 
 
 class BhBatch(ctypes.Structure):
@@ -270,6 +271,14 @@ def lib() -> ctypes.CDLL:
         L.bh_keys_clear.restype = i32
         L.bh_keys_count.argtypes = [i32, i32, ctypes.POINTER(sz)]
         L.bh_keys_count.restype = i32
+        L.bh_keys384_reserve.argtypes = [i32, sz]
+        L.bh_keys384_reserve.restype = i32
+        L.bh_keys384_register.argtypes = [i32, vp, sz, vp]
+        L.bh_keys384_register.restype = i32
+        L.bh_keys384_clear.argtypes = [i32]
+        L.bh_keys384_clear.restype = i32
+        L.bh_keys384_count.argtypes = [i32, ctypes.POINTER(sz)]
+        L.bh_keys384_count.restype = i32
         L.bh_bdls_preverify.argtypes = [i32, vp, vp, vp, sz, vp, sz, u32, vp, vp, sz,
                                         ctypes.POINTER(sz)]
         L.bh_bdls_preverify.restype = i32

@@ -244,6 +244,21 @@ class HipCSP:
         return verify_packed(*pack_records(keys, signatures, messages),
                              flags=self._flags | flag, curve=batch_curve(keys))
 
+    def register_keys_p384(self, keys: Sequence[ECDSAPublicKey], device: int = -1) -> np.ndarray:
+        """bh_keys384_register: build and keep the fixed-base tables of P-384 keys
+        that will verify again and again (the MSP identity cache, msp/cache/cache.go;
+        the BDLS participant set). Returns one status byte per key: 0 registered
+        or already present, 7 not a point of P-384, 255 registry full. Results of
+        verification never depend on it."""
+        for k in keys:
+            if not isinstance(k, ECDSAPublicKey) or k.curve != "P-384":
+                raise BCCSPError(-1, f"Unsupported key for the P-384 registry [{k}]")
+        status = np.zeros(len(keys), np.uint8)
+        if len(keys):
+            raw = b"".join(k.raw() for k in keys)
+            _lib.check(_lib.lib().bh_keys384_register(device, raw, len(keys), status.ctypes.data))
+        return status
+
     def identity_verify(self, k, msg: bytes, sig: bytes, family: str = "SHA2",
                         hash: str | None = None) -> None:
         """identity.Verify: raises on error or invalid signature (returns None if valid)."""

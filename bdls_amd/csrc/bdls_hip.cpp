@@ -28,6 +28,7 @@
 
 #include "../../include/bdls_hip.h"
 #include "verify.h"
+#include "keys384.h"
 #include "verify384.h"
 #include "pack.h"
 #include "shard.h"
@@ -50,6 +51,13 @@ hipError_t launch_gtab384_build(uint32_t* gtab, hipStream_t s);
 hipError_t launch_sha512(int out_bytes, const uint8_t* msg, const uint64_t* msg_off,
                          const uint32_t* msg_len, uint32_t n, uint8_t* dig, uint64_t* off,
                          uint32_t* len, hipStream_t s);
+hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg384& g,
+                                 const Plan384& pl, const uint32_t* gtab, uint32_t n,
+                                 uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipStream_t aux,
+                                 hipEvent_t fork, hipEvent_t join, hipEvent_t* ev);
+hipError_t launch_keys384_register(const KeyReg384& g, const uint8_t* pub, uint32_t n,
+                                   uint8_t* status, uint32_t* fresh, uint32_t* bases,
+                                   hipStream_t s);
 hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* gtab, uint32_t n,
                             uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev);
 size_t expand_temp_bytes(uint32_t m);
@@ -224,7 +232,12 @@ struct Dev {
   uint32_t* gtab384 = nullptr;  // fixed-base table of G
   DevBuf ws384;                 // Work384
   DevBuf in384, out384;         // bh_verify: one chunk's inputs / bitmap words + reasons
-  hipEvent_t ev384[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev384[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // bh_keys384_*: the P-384 key registry (allocated by reserve or the first register)
+  DevBuf reg384_mem;
+  bh::KeyReg384 reg384{};    // cap == 0: not allocated
+  size_t reg384_count = 0;   // keys registered (the device's count, read back by register)
+  DevBuf kb384;              // bh_keys384_register: keys, status, fresh slots, window bases
   // BH_F_HASH_SHA384 / BH_F_HASH_SHA512 (allocated at the device's first such call, under mu)
   DevBuf dig512;  // one chunk's digests, offsets and lengths: the curve pass's digest batch
   hipEvent_t ev512[2] = {nullptr, nullptr};
@@ -406,6 +419,42 @@ int reg_alloc(Dev& d, int curve, size_t cap) {
   return BH_OK;
 }
 
+// bh_keys384_register without a reserve: 256 keys of 161,280 + 96 bytes, 39.4 MiB.
+constexpr size_t kDefaultReg384Cap = 256;
+
+// (Re)allocate and clear the P-384 key registry (caller holds d.mu, device set).
+int reg384_alloc(Dev& d, size_t cap) {
+  if (cap == 0 || cap > (size_t(1) << 16))
+    return fail(BH_E_INVALID, "P-384 registry capacity out of range (1 .. 65536)");
+  const size_t hc = pow2_at_least(2 * cap);
+  const size_t bytes = round256(hc * 4) + round256(cap * 96) +
+                       round256(cap * (size_t)bh::kKTab384Words * 4) + 256;
+  if (int rc = sync_lanes(d)) return rc;
+  HIPCHK(hipDeviceSynchronize());  // a pass on a caller's stream may still read the tables
+  d.reg384_mem.release();
+  d.reg384 = bh::KeyReg384{};
+  d.reg384_count = 0;
+  if (int rc = d.reg384_mem.ensure(bytes)) return rc;
+  char* p = (char*)d.reg384_mem.p;
+  auto take = [&](size_t b) {
+    char* q = p;
+    p += round256(b);
+    return q;
+  };
+  bh::KeyReg384 g{};
+  g.cap = (uint32_t)cap;
+  g.hc = (uint32_t)hc;
+  g.bucket = (uint32_t*)take(hc * 4);
+  g.keys = (uint32_t*)take(cap * 96);
+  g.tables = (uint32_t*)take(cap * (size_t)bh::kKTab384Words * 4);
+  g.count = (uint32_t*)take(4);
+  HIPCHK(hipMemsetAsync(g.bucket, 0, hc * 4, d.stream));
+  HIPCHK(hipMemsetAsync(g.count, 0, 4, d.stream));
+  HIPCHK(hipStreamSynchronize(d.stream));
+  d.reg384 = g;
+  return BH_OK;
+}
+
 // Host waits on a pass block (hipEventBlockingSync) unless BH_BLOCKING_SYNC=0.
 // Measured (tools/sv_tail.py): HIP's default spin-wait
 // let 256 coalesced Verify callers exhaust the box's 16-CPU cgroup quota --
@@ -495,6 +544,10 @@ void dev_free(Dev& d) {
   d.ws384.release();
   d.in384.release();
   d.out384.release();
+  d.reg384_mem.release();
+  d.reg384 = bh::KeyReg384{};
+  d.reg384_count = 0;
+  d.kb384.release();
   d.dig512.release();
   for (auto& e : d.ev512) {
     if (e) (void)hipEventDestroy(e);
@@ -1740,8 +1793,12 @@ size_t p384_chunk() {
   return chunk;
 }
 
+// Bytes of a pass's workspace for ns records: Work384, then Plan384 (slot and
+// the two index lists, 12 bytes per record, and the two counts).
+size_t ws384_bytes(size_t ns) { return ns * (bh::kWork384Words * 4 + 1 + 12) + 256 * 14; }
+
 // Workspace and G table of the device's P-384 pass (caller holds d.mu, device set).
-int p384_setup(Dev& d, size_t m, bh::Work384* w) {
+int p384_setup(Dev& d, size_t m, bh::Work384* w, bh::Plan384* pl) {
   if (!d.gtab384) {
     uint32_t* g = nullptr;
     hipError_t e = hipMalloc(&g, bh::kGTab384Words * 4);
@@ -1765,7 +1822,7 @@ int p384_setup(Dev& d, size_t m, bh::Work384* w) {
     d.gtab384 = g;
   }
   const size_t ns = round64(m);
-  if (int rc = d.ws384.ensure(ns * (bh::kWork384Words * 4 + 1) + 256 * 10)) return rc;
+  if (int rc = d.ws384.ensure(ws384_bytes(ns))) return rc;
   char* p = (char*)d.ws384.p;
   auto take = [&](size_t bytes) {
     char* q = p;
@@ -1783,6 +1840,10 @@ int p384_setup(Dev& d, size_t m, bh::Work384* w) {
   w->r2m = (uint32_t*)take(56 * ns);
   w->qtab = (uint32_t*)take((size_t)8 * 3 * 56 * ns);
   w->st = (uint8_t*)take(ns);
+  pl->slot = (uint32_t*)take(4 * ns);
+  pl->tab_list = (uint32_t*)take(4 * ns);
+  pl->lad_list = (uint32_t*)take(4 * ns);
+  pl->cnt = (uint32_t*)take(8);
   return BH_OK;
 }
 
@@ -1796,15 +1857,38 @@ int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bi
   for (size_t base = 0; base < n; base += chunk) {
     const size_t m = std::min(chunk, n - base);
     bh::Work384 w;
+    bh::Plan384 pl;
     // the workspace may be reallocated: everything that used it has to be done
     if (int rc = sync_lanes(d)) return rc;
-    if (round64(m) * (bh::kWork384Words * 4 + 1) + 2560 > d.ws384.cap)
-      HIPCHK(hipDeviceSynchronize());
-    if (int rc = p384_setup(d, m, &w)) return rc;
+    if (ws384_bytes(round64(m)) > d.ws384.cap) HIPCHK(hipDeviceSynchronize());
+    if (int rc = p384_setup(d, m, &w, &pl)) return rc;
     HIPCHK(wait_lanes(d, s));
     const bh::In384 in{b->pub + base * 96, b->sig,     b->sig_off + base, b->sig_len + base,
                        b->msg,             b->msg_off + base, b->msg_len + base,
                        flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256)};
+    if (d.reg384_count) {  // keys registered: each chunk plans its own two routes
+      HIPCHK(bh::launch_verify384_keys(in, w, d.reg384, pl, d.gtab384, (uint32_t)m,
+                                       bitmap + base / 64, reason + base, s, d.aux, d.fork,
+                                       d.join, t ? d.ev384 : nullptr));
+      if (t) {
+        HIPCHK(hipEventSynchronize(d.ev384[6]));
+        // the two routes start together after the plan (ev384[3]) and overlap:
+        // keycomb_ms and build_ladder_ms are each route's own time from there
+        float ms[5];
+        for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], d.ev384[k], d.ev384[k + 1]));
+        HIPCHK(hipEventElapsedTime(&ms[4], d.ev384[3], d.ev384[5]));
+        uint32_t cnt[2] = {0, 0};
+        HIPCHK(hipMemcpy(cnt, pl.cnt, 8, hipMemcpyDeviceToHost));
+        t->prep_ms += ms[0];
+        t->inv_ms += ms[1];
+        t->plan_ms += ms[2];
+        t->keycomb_ms += ms[3];
+        t->build_ladder_ms += ms[4];
+        t->n_keycomb += cnt[0];
+        t->n_ladder += (uint32_t)m - cnt[0];
+      }
+      continue;
+    }
     HIPCHK(bh::launch_verify384(in, w, d.gtab384, (uint32_t)m, bitmap + base / 64, reason + base,
                                 s, t ? d.ev384 : nullptr));
     if (t) {
@@ -2858,6 +2942,70 @@ int bh_keys_count(int device, int curve, size_t* count) {
       HIPCHK(hipMemcpy(&v, g.count, 4, hipMemcpyDeviceToHost));
       c = std::min<size_t>(v, g.cap);
     }
+    *count = first ? c : std::min(*count, c);  // -1: keys present on every device
+    first = false;
+    return BH_OK;
+  });
+}
+
+// ---- P-384 key registry ------------------------------------------------------
+int bh_keys384_reserve(int device, size_t capacity) {
+  return for_devices(device, [&](Dev& d) { return reg384_alloc(d, capacity); });
+}
+
+int bh_keys384_register(int device, const uint8_t* pub, size_t n, uint8_t* status) {
+  if (n && !pub) return fail(BH_E_INVALID, "null pub");
+  if (status) std::memset(status, 0, n);
+  constexpr size_t kRegChunk = 1024;  // 16 KiB of window bases per key in flight
+  std::vector<uint8_t> st(std::min(n, kRegChunk));
+  return for_devices(device, [&](Dev& d) -> int {
+    if (n && d.reg384.cap == 0)
+      if (int rc = reg384_alloc(d, kDefaultReg384Cap)) return rc;
+    for (size_t lo = 0; lo < n; lo += kRegChunk) {
+      const size_t m = std::min(kRegChunk, n - lo);
+      const size_t bases = m * bh::kG384Win * bh::kBase384Words * 4;
+      if (int rc = d.kb384.ensure(round256(m * 96) + round256(m) + round256(4 * (m + 1)) + bases))
+        return rc;
+      uint8_t* dpub = (uint8_t*)d.kb384.p;
+      uint8_t* dst = dpub + round256(m * 96);
+      uint32_t* fresh = (uint32_t*)(dst + round256(m));
+      uint32_t* dbases = (uint32_t*)((uint8_t*)fresh + round256(4 * (m + 1)));
+      hipStream_t s = d.stream;
+      // behind every lane's work and every P-384 pass, whatever stream it ran on
+      if (int rc = sync_lanes(d)) return rc;
+      HIPCHK(hipMemcpyAsync(dpub, pub + lo * 96, m * 96, hipMemcpyHostToDevice, s));
+      HIPCHK(bh::launch_keys384_register(d.reg384, dpub, (uint32_t)m, dst, fresh, dbases, s));
+      uint32_t cnt = 0;
+      HIPCHK(hipMemcpyAsync(st.data(), dst, m, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(&cnt, d.reg384.count, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      d.reg384_count = std::min<size_t>(cnt, d.reg384.cap);
+      if (status)
+        for (size_t i = 0; i < m; i++) status[lo + i] = std::max(status[lo + i], st[i]);
+    }
+    return BH_OK;
+  });
+}
+
+int bh_keys384_clear(int device) {
+  return for_devices(device, [&](Dev& d) -> int {
+    const bh::KeyReg384& g = d.reg384;
+    if (g.cap == 0) return BH_OK;
+    if (int rc = sync_lanes(d)) return rc;
+    HIPCHK(hipMemsetAsync(g.bucket, 0, (size_t)g.hc * 4, d.stream));
+    HIPCHK(hipMemsetAsync(g.count, 0, 4, d.stream));
+    HIPCHK(hipStreamSynchronize(d.stream));
+    d.reg384_count = 0;
+    return BH_OK;
+  });
+}
+
+int bh_keys384_count(int device, size_t* count) {
+  if (!count) return fail(BH_E_INVALID, "null count");
+  *count = 0;
+  bool first = true;
+  return for_devices(device, [&](Dev& d) -> int {
+    const size_t c = d.reg384_count;  // register and clear are synchronous: the device's count
     *count = first ? c : std::min(*count, c);  // -1: keys present on every device
     first = false;
     return BH_OK;

@@ -52,7 +52,8 @@ BH_HD bool j384_on_curve(const uint32_t x[14], const uint32_t y[14]) {
 }
 
 // A = 2A (dbl-2001-b). In: X, Y, Z < 20p. Out: X, Y < 18p, Z < 6p.
-inline BH_HDNI void j384_dbl(J384* A) {
+// j384_dbl_inl is the body; j384_dbl the shared out-of-line copy (see j384_madd).
+BH_HD void j384_dbl_inl(J384* A) {
   if (A->inf) return;
   uint32_t delta[14], gamma[14], beta[14], alpha[14], t0[14], t1[14];
   f384_sqr<P384>(delta, A->z);           // 20*20 = 400 [3p]
@@ -74,10 +75,16 @@ inline BH_HDNI void j384_dbl(J384* A) {
   f384_muls<8>(t1, t1);                  // [16p]
   f384_sub<P384, 16>(A->y, t0, t1);      // Y3 = alpha (4 beta - X3) + 16p - 8 gamma^2 [18p]
 }
+inline BH_HDNI void j384_dbl(J384* A) { j384_dbl_inl(A); }
 
 // A = A + (x2, y2), the affine point negated when neg. x2, y2 < 2p.
 // In: A < 20p. Out: X < 9p, Y < 4p, Z < 3p.
-inline BH_HDNI void j384_madd(J384* A, const uint32_t x2[14], const uint32_t y2in[14], uint32_t neg) {
+// j384_madd_body is the body, inlined into its caller. j384_madd is the shared
+// out-of-line copy (its rare doubling a call as well); j384_madd_inl has no
+// call in it: k384_keywin (keys384.h) does nothing but mixed additions and
+// keeps its one point in registers, at its own register count.
+template <bool INL>
+BH_HD void j384_madd_body(J384* A, const uint32_t x2[14], const uint32_t y2in[14], uint32_t neg) {
   uint32_t y2[14];
   if (neg) f384_sub<P384, 2>(y2, P384::km[0], y2in);  // 2p - y [2p]
   else f384_copy(y2, y2in);
@@ -96,7 +103,8 @@ inline BH_HDNI void j384_madd(J384* A, const uint32_t x2[14], const uint32_t y2i
   if (f384_is_zero_small<P384, 3>(z3)) { // H = 0 mod p (Z1 is not): same x
     if (f384_is_zero<P384>(r)) {
       j384_set_affine(A, x2, y2);        // A == T: 2T
-      j384_dbl(A);
+      if (INL) j384_dbl_inl(A);
+      else j384_dbl(A);
     } else {
       A->inf = 1;                        // A == -T
     }
@@ -114,6 +122,12 @@ inline BH_HDNI void j384_madd(J384* A, const uint32_t x2[14], const uint32_t y2i
   f384_mul<P384>(v, A->y, hhh);          // 40 [2p]
   f384_sub<P384, 2>(A->y, t, v);         // Y3 [4p]
   f384_copy(A->z, z3);                   // Z3 = Z1 H [3p]
+}
+inline BH_HDNI void j384_madd(J384* A, const uint32_t x2[14], const uint32_t y2in[14], uint32_t neg) {
+  j384_madd_body<false>(A, x2, y2in, neg);
+}
+BH_HD void j384_madd_inl(J384* A, const uint32_t x2[14], const uint32_t y2in[14], uint32_t neg) {
+  j384_madd_body<true>(A, x2, y2in, neg);
 }
 
 // A = A + T, T negated when neg. In: both < 20p. Out: X < 8p, Y < 4p, Z < 2p.

@@ -265,6 +265,20 @@ BH_HD void gtab384_entry(uint32_t t, uint32_t* gtab) {
 // Bits [4j, 4j + 4) of a 13-word integer.
 BH_HD uint32_t nib13(const uint32_t v[13], int j) { return (v[j >> 3] >> (4 * (j & 7))) & 15u; }
 
+// x(A) mod n == r for record i: x = r, or x = r + n when that is below p.
+// False at infinity.
+BH_HD bool x_check384(const Work384& w, uint32_t i, const J384* A) {
+  if (A->inf) return false;
+  uint32_t rm[14];
+  ldw<14>(rm, w.rm, i, w.ns);
+  if (j384_x_equals(A, rm)) return true;
+  if (w.st[i] & ST384_R2OK) {  // x in [n, p): r + n
+    ldw<14>(rm, w.r2m, i, w.ns);
+    return j384_x_equals(A, rm);
+  }
+  return false;
+}
+
 // Record i: true iff x(u1 G + u2 Q) mod n == r (false at infinity).
 BH_HD bool stage384_ladder(const Work384& w, const uint32_t* gtab, uint32_t i) {
   uint32_t qx[14], qy[14];
@@ -322,15 +336,7 @@ BH_HD bool stage384_ladder(const Work384& w, const uint32_t* gtab, uint32_t i) {
     for (int k = 0; k < 14; k++) { gx[k] = g[k]; gy[k] = g[14 + k]; }
     j384_madd(&A, gx, gy, 0);
   }
-  if (A.inf) return false;
-  uint32_t rm[14];
-  ldw<14>(rm, w.rm, i, w.ns);
-  if (j384_x_equals(&A, rm)) return true;
-  if (w.st[i] & ST384_R2OK) {  // x in [n, p): r + n
-    ldw<14>(rm, w.r2m, i, w.ns);
-    return j384_x_equals(&A, rm);
-  }
-  return false;
+  return x_check384(w, i, &A);
 }
 
 }  // namespace bh

@@ -8,7 +8,17 @@
 //   k384_inv     1 lane/chunk    s^-1 by Montgomery's trick, u1, u2
 //   k384_ladder  1 lane/record   u2 Q (signed window) + u1 G (table), x check
 //   k384_bitmap  1 lane/record   validity bitmap from the reason bytes
-#include "verify384.h"
+//
+// With keys in the registry (bh_keys384_*, keys384.h) a pass routes its records:
+//   k384_plan         1 lane/record   registry lookup, the two index lists
+//   k384_keywin       1 lane/record   table route: u2 Q and u1 G from tables
+//   k384_ladder_list  1 lane/record   k384_ladder over the other list
+// and bh_keys384_register runs
+//   k384_keys_import  1 lane/key      key_import384's verdict
+//   k384_keys_insert  1 lane          the registry's one writer
+//   k384_keytab_bases 1 lane/key      the doubling chain, 96 window bases
+//   k384_keytab_rows  1 lane/window   15 affine entries, one inversion
+#include "keys384.h"
 
 using namespace bh;
 
@@ -44,6 +54,87 @@ __global__ __launch_bounds__(64) void k384_ladder(Work384 w, const uint32_t* __r
   reason[i] = stage384_ladder(w, gtab, i) ? (uint8_t)R_OK : (uint8_t)R_MATH;
 }
 
+__global__ __launch_bounds__(64) void k384_plan(In384 in, Work384 w, KeyReg384 g, uint32_t n,
+                                                Plan384 pl) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t slot = i < n ? stage384_plan(in, w, g, i) : kNoSlot384;
+  const bool hit = slot != kNoSlot384, miss = i < n && !hit;
+  // one route per wave downstream: each wave appends its records to the two lists
+  const uint64_t mh = __ballot(hit), mm = __ballot(miss);
+  uint32_t bh_ = 0, bm_ = 0;
+  if (lane == 0) {
+    if (mh) bh_ = atomicAdd(&pl.cnt[0], (uint32_t)__popcll(mh));
+    if (mm) bm_ = atomicAdd(&pl.cnt[1], (uint32_t)__popcll(mm));
+  }
+  bh_ = __shfl(bh_, 0);
+  bm_ = __shfl(bm_, 0);
+  const uint64_t below = (1ull << lane) - 1;
+  if (hit) {
+    pl.slot[i] = slot;
+    pl.tab_list[bh_ + (uint32_t)__popcll(mh & below)] = i;
+  } else if (miss) {
+    pl.lad_list[bm_ + (uint32_t)__popcll(mm & below)] = i;
+  }
+}
+
+__global__ __launch_bounds__(64) void k384_keywin(Work384 w, KeyReg384 g, Plan384 pl,
+                                                  const uint32_t* __restrict__ gtab,
+                                                  uint8_t* __restrict__ reason) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= pl.cnt[0]) return;
+  const uint32_t i = pl.tab_list[t];
+  const uint32_t* qtab = g.tables + (size_t)pl.slot[i] * kKTab384Words;
+  reason[i] = stage384_keywin(w, qtab, gtab, i) ? (uint8_t)R_OK : (uint8_t)R_MATH;
+}
+
+__global__ __launch_bounds__(64) void k384_ladder_list(Work384 w, Plan384 pl,
+                                                       const uint32_t* __restrict__ gtab,
+                                                       uint8_t* __restrict__ reason) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= pl.cnt[1]) return;
+  const uint32_t i = pl.lad_list[t];
+  const uint8_t st = w.st[i] & 0x7fu;
+  if (st != R_OK) {
+    reason[i] = st;
+    return;
+  }
+  reason[i] = stage384_ladder(w, gtab, i) ? (uint8_t)R_OK : (uint8_t)R_MATH;
+}
+
+__global__ __launch_bounds__(64) void k384_keys_import(const uint8_t* __restrict__ pub, uint32_t n,
+                                                       uint8_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t qx[14], qy[14];
+  status[i] = key_import384(pub + (size_t)i * 96, qx, qy) ? (uint8_t)0 : (uint8_t)R_BAD_KEY;
+}
+
+__global__ __launch_bounds__(64) void k384_keys_insert(KeyReg384 g, const uint8_t* pub, uint32_t n,
+                                                       uint8_t* status, uint32_t* fresh,
+                                                       uint32_t* nfresh) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) keys384_insert(g, pub, n, status, fresh, nfresh);
+}
+
+__global__ __launch_bounds__(64) void k384_keytab_bases(KeyReg384 g, const uint32_t* __restrict__ fresh,
+                                                        const uint32_t* __restrict__ nfresh,
+                                                        uint32_t* __restrict__ bases) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= *nfresh) return;
+  keytab384_bases(g, fresh[t], bases + (size_t)t * kG384Win * kBase384Words);
+}
+
+__global__ __launch_bounds__(64) void k384_keytab_rows(KeyReg384 g, const uint32_t* __restrict__ fresh,
+                                                       const uint32_t* __restrict__ nfresh,
+                                                       const uint32_t* __restrict__ bases) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t key = t / kG384Win, win = t % kG384Win;
+  if (key >= *nfresh) return;
+  keytab384_window(bases + (size_t)t * kBase384Words,
+                   g.tables + (size_t)fresh[key] * kKTab384Words +
+                       (size_t)win * kG384Ent * kG384Words);
+}
+
 __global__ __launch_bounds__(256) void k384_bitmap(const uint8_t* __restrict__ reason, uint32_t n,
                                                    uint64_t* __restrict__ bitmap) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,6 +167,58 @@ hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* g
   hipLaunchKernelGGL(k384_ladder, grd, blk, 0, s, w, gtab, n, reason);
   hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
   if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+// The pass with keys in the registry. pl.cnt is cleared here; the list kernels
+// are launched for n lanes and read their list's length on the device. The two
+// routes run side by side: the table route on aux (fork / join order it after
+// the plan and before the bitmap), the ladder on s, whose one wave per SIMD
+// leaves registers for the table route's waves.
+// ev (optional): 7 events: prep, inverse, plan | end of the table route (on
+// aux) | end of the ladder (on s) | end of the bitmap.
+hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg384& g,
+                                 const Plan384& pl, const uint32_t* gtab, uint32_t n,
+                                 uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipStream_t aux,
+                                 hipEvent_t fork, hipEvent_t join, hipEvent_t* ev) {
+  if (n == 0) return hipSuccess;
+  hipError_t e;
+  const dim3 blk(64), grd((n + 63) / 64);
+  if ((e = hipMemsetAsync(pl.cnt, 0, 8, s)) != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_prep, grd, blk, 0, s, in, w, n);
+  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+  const uint32_t stride = (n + kInvChunk384 - 1) / kInvChunk384;
+  hipLaunchKernelGGL(k384_inv, dim3((stride + 63) / 64), blk, 0, s, w, stride, n);
+  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_plan, grd, blk, 0, s, in, w, g, n, pl);
+  if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
+  if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_keywin, grd, blk, 0, aux, w, g, pl, gtab, reason);
+  if (ev && (e = hipEventRecord(ev[4], aux)) != hipSuccess) return e;
+  if ((e = hipEventRecord(join, aux)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_ladder_list, grd, blk, 0, s, w, pl, gtab, reason);
+  if (ev && (e = hipEventRecord(ev[5], s)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
+  if (ev && (e = hipEventRecord(ev[6], s)) != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+// bh_keys384_register's kernels for n keys at pub (device): verdicts, the
+// serial insert, then the tables of the slots it handed out. bases: n * 96 *
+// kBase384Words words; fresh: n + 1 words (the last is the count).
+hipError_t launch_keys384_register(const KeyReg384& g, const uint8_t* pub, uint32_t n,
+                                   uint8_t* status, uint32_t* fresh, uint32_t* bases,
+                                   hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  uint32_t* nfresh = fresh + n;
+  hipLaunchKernelGGL(k384_keys_import, dim3((n + 63) / 64), dim3(64), 0, s, pub, n, status);
+  hipLaunchKernelGGL(k384_keys_insert, dim3(1), dim3(64), 0, s, g, pub, n, status, fresh, nfresh);
+  hipLaunchKernelGGL(k384_keytab_bases, dim3((n + 63) / 64), dim3(64), 0, s, g, fresh, nfresh, bases);
+  const uint32_t t = n * (uint32_t)kG384Win;
+  hipLaunchKernelGGL(k384_keytab_rows, dim3((t + 63) / 64), dim3(64), 0, s, g, fresh, nfresh, bases);
   return hipGetLastError();
 }
 

@@ -680,6 +680,39 @@ int bh_keys_register(int device, int curve, const uint8_t *pub, size_t n, uint8_
 int bh_keys_clear(int device, int curve);
 int bh_keys_count(int device, int curve, size_t *count);
 
+/* ---- key registry, BH_CURVE_P384 ---------------------------------------------
+ * The P-384 counterpart of the registry above, with entry points of its own:
+ * 96-byte keys, and per key a fixed-base table of 96 windows x 15 multiples of
+ * Q (161,280 bytes in HBM, plus the 96 key bytes). A P-384 record whose key is
+ * registered skips the ladder: u2 Q and u1 G are table additions, about 2,000
+ * field products against the ladder's 5,600. As above this mirrors the
+ * reference's long-lived identities -- the MSP identity cache
+ * (msp/cache/cache.go) for Fabric, the fixed participant set
+ * (consensus.go:456-466, Config.Participants) for BDLS -- and results never
+ * depend on it: same bitmap and reasons with or without, in bh_verify and
+ * bh_verify_dev, with any BH_F_HASH_* flag. BH_F_KEEP_KEYS stays ignored for
+ * P-384: tables are built by bh_keys384_register alone, never by a pass
+ * (bh_timing.n_keytables stays 0; n_keycomb counts the records that took the
+ * table route, plan_ms the lookup, keycomb_ms the table route, build_ladder_ms
+ * the ladder; the two routes run side by side after the lookup, so these two
+ * times overlap). bh_keys_* above keep refusing BH_CURVE_P384.
+ * device: -1 means every initialised device. A null pub with n > 0 or a null
+ * count is BH_E_INVALID; otherwise, before bh_init, BH_E_NOT_INIT.
+ * capacity: keys per device, 1 .. 65536; reserving replaces (and empties) the
+ * registry. bh_keys384_register reserves 256 (39.4 MiB) when nothing was
+ * reserved before. Entries persist until bh_keys384_clear or bh_shutdown; once
+ * full, new keys stay on the ladder. */
+int bh_keys384_reserve(int device, size_t capacity);
+/* Import and register n keys (host pointer, n * 96 bytes X || Y). status
+ * (optional, n bytes): 0 registered (or already present), BH_R_BAD_KEY not a
+ * point of P-384 (X or Y >= p, or off the curve: the checks a pass makes),
+ * 255 registry full. Synchronous: under the device lock, behind every lane's
+ * work and every P-384 pass; the tables are complete when it returns. */
+int bh_keys384_register(int device, const uint8_t *pub, size_t n, uint8_t *status);
+int bh_keys384_clear(int device);
+/* Keys registered; with device -1 the minimum over the devices. */
+int bh_keys384_count(int device, size_t *count);
+
 #ifdef __cplusplus
 }
 #endif
