@@ -11,7 +11,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/bdls_hip.h
 
 all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so \
      tests/native/build/libhostsim384.so tests/native/build/libhostsim384k.so \
-     tests/native/build/libhostsim512.so $(LIB)/csp_load
+     tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -63,6 +63,12 @@ tests/native/build/libhostsim384.so: tests/native/hostsim384.cpp $(HDRS)
 
 # (hostsim384_keys.cpp includes hostsim384.cpp and adds the P-384 key registry's entries)
 tests/native/build/libhostsim384k.so: tests/native_p384keys/hostsim384_keys.cpp \
+                                      tests/native/hostsim384.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
+
+# (hostsim384_seg.cpp includes hostsim384.cpp and adds the pass over two-span records)
+tests/native/build/libhostsim384s.so: tests/native_p384seg/hostsim384_seg.cpp \
                                       tests/native/hostsim384.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread

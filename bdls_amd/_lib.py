@@ -41,6 +41,7 @@ EXPORTS = (
     "bh_batch_verify", "bh_batch_verify_submit", "bh_batch_verify_ptrs",
     "bh_batch_verify_ptrs_submit", "bh_pack_stats", "bh_curve_key_bytes", "bh_verify_x509_ex",
     "bh_keys384_reserve", "bh_keys384_register", "bh_keys384_clear", "bh_keys384_count",
+    "bh_verify_mixed",
 )
 KEY_FULL = 255  # bh_keys_register / bh_keys384_register status: registry full
 
@@ -55,6 +56,14 @@ class BhBatch(ctypes.Structure):
         ("msg_off", ctypes.c_void_p),
         ("msg_len", ctypes.c_void_p),
     ]
+
+
+class BhMBatch(ctypes.Structure):
+    """include/bdls_hip.h bh_mbatch: records of either NIST curve (a curve byte
+    and a key offset per record) with optional second message spans."""
+    _fields_ = [(f, ctypes.c_void_p) for f in (
+        "curve", "pub", "pub_off", "sig", "sig_off", "sig_len", "msg", "msg_off", "msg_len",
+        "msg2_off", "msg2_len")]
 
 
 class BhCBatch(ctypes.Structure):
@@ -173,6 +182,8 @@ def lib() -> ctypes.CDLL:
         L.bh_verify.restype = i32
         L.bh_verify_2seg.argtypes = [i32, ctypes.POINTER(BhBatch), vp, vp, sz, u32, vp, vp]
         L.bh_verify_2seg.restype = i32
+        L.bh_verify_mixed.argtypes = [ctypes.POINTER(BhMBatch), sz, u32, vp, vp]
+        L.bh_verify_mixed.restype = i32
         L.bh_verify_submit.argtypes = [i32, ctypes.POINTER(BhBatch), sz, u32, vp, vp,
                                        ctypes.POINTER(vp)]
         L.bh_verify_submit.restype = i32

@@ -175,6 +175,26 @@ def verify_packed(pub, sig, sig_off, sig_len, msg, msg_off, msg_len, flags: int 
     return valid, reason[:n]
 
 
+def verify_mixed(curve, pub, pub_off, sig, sig_off, sig_len, msg, msg_off, msg_len,
+                 msg2_off=None, msg2_len=None, flags: int = 0):
+    """Host-buffer batch of P-256 and P-384 records through bh_verify_mixed:
+    curve u8[n] (BH_CURVE_P256 / BH_CURVE_P384), record i's key at
+    pub[pub_off[i]:], optional second message spans (both or neither).
+    Returns (valid bool[n], reason u8[n])."""
+    _lib.ensure_init()
+    n = len(sig_len)
+    bitmap = np.zeros((n + 7) // 8 or 1, dtype=np.uint8)
+    reason = np.zeros(n or 1, dtype=np.uint8)
+    b = _lib.BhMBatch(_arr(curve), _arr(pub), _arr(pub_off), _arr(sig), _arr(sig_off),
+                      _arr(sig_len), _arr(msg), _arr(msg_off), _arr(msg_len),
+                      None if msg2_off is None else msg2_off.ctypes.data,
+                      None if msg2_len is None else msg2_len.ctypes.data)
+    _lib.check(_lib.lib().bh_verify_mixed(ctypes.byref(b), n, flags, bitmap.ctypes.data,
+                                          reason.ctypes.data))
+    valid = np.unpackbits(bitmap, bitorder="little")[:n].astype(bool)
+    return valid, reason[:n]
+
+
 class HipCSP:
     """The `bccsp/hip` provider's verify/hash surface (embeds sw semantics)."""
 

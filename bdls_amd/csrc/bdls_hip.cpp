@@ -74,6 +74,9 @@ thread_local std::string g_err;
 // Device batches launched (one per run_dev call, one per latency-path batch)
 // and the records they carried, over the process (bh_device_stats).
 std::atomic<uint64_t> g_dev_batches{0}, g_dev_records{0};
+// bumped whenever a P-384 key registry loses its keys (clear, re-reserve,
+// shutdown): whoever remembers which keys it registered forgets them then
+std::atomic<uint64_t> g_reg384_gen{0};
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -434,6 +437,7 @@ int reg384_alloc(Dev& d, size_t cap) {
   d.reg384_mem.release();
   d.reg384 = bh::KeyReg384{};
   d.reg384_count = 0;
+  g_reg384_gen.fetch_add(1, std::memory_order_relaxed);
   if (int rc = d.reg384_mem.ensure(bytes)) return rc;
   char* p = (char*)d.reg384_mem.p;
   auto take = [&](size_t b) {
@@ -547,6 +551,7 @@ void dev_free(Dev& d) {
   d.reg384_mem.release();
   d.reg384 = bh::KeyReg384{};
   d.reg384_count = 0;
+  g_reg384_gen.fetch_add(1, std::memory_order_relaxed);
   d.kb384.release();
   d.dig512.release();
   for (auto& e : d.ev512) {
@@ -1849,9 +1854,11 @@ int p384_setup(Dev& d, size_t m, bh::Work384* w, bh::Plan384* pl) {
 
 // The P-384 passes of a device-resident batch on stream s, after every lane's
 // work (one workspace per device). Caller holds d.mu, device set, and counts
-// the batch for bh_device_stats (one per call of the C ABI).
+// the batch for bh_device_stats (one per call of the C ABI). msg2_off /
+// msg2_len (device, both or neither): the records' second spans, fused modes.
 int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bitmap,
-               uint8_t* reason, hipStream_t s, bh_timing* t) {
+               uint8_t* reason, hipStream_t s, bh_timing* t, const uint64_t* msg2_off = nullptr,
+               const uint32_t* msg2_len = nullptr) {
   if (t) *t = bh_timing{};
   const size_t chunk = p384_chunk();
   for (size_t base = 0; base < n; base += chunk) {
@@ -1865,7 +1872,8 @@ int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bi
     HIPCHK(wait_lanes(d, s));
     const bh::In384 in{b->pub + base * 96, b->sig,     b->sig_off + base, b->sig_len + base,
                        b->msg,             b->msg_off + base, b->msg_len + base,
-                       flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256)};
+                       flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256),
+                       msg2_off ? msg2_off + base : nullptr, msg2_len ? msg2_len + base : nullptr};
     if (d.reg384_count) {  // keys registered: each chunk plans its own two routes
       HIPCHK(bh::launch_verify384_keys(in, w, d.reg384, pl, d.gtab384, (uint32_t)m,
                                        bitmap + base / 64, reason + base, s, d.aux, d.fork,
@@ -1972,9 +1980,12 @@ int run_dev_wide(Dev& d, int curve, const bh_batch* b, size_t n, uint32_t flags,
 
 // bh_verify for BH_CURVE_P384, and for either curve with BH_F_HASH_SHA384 /
 // BH_F_HASH_SHA512: the first initialised device alone; upload, run and
-// download chunk by chunk, synchronously.
+// download chunk by chunk, synchronously. msg2_off / msg2_len (host, both or
+// neither; P-384 with a fused hash only): the records' second spans, which
+// index b->msg like the first; a chunk uploads the union of both spans' ranges.
 int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
-                   uint8_t* reason) {
+                        uint8_t* reason, const uint64_t* msg2_off = nullptr,
+                        const uint32_t* msg2_len = nullptr) {
   const size_t kb = curve == BH_CURVE_P384 ? 96 : 64;
   std::vector<Dev*> ds = all_devs();
   if (ds.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
@@ -1986,7 +1997,7 @@ int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, 
   const size_t chunk = p384_chunk();
   g_dev_batches.fetch_add(1, std::memory_order_relaxed);  // one batch, however many chunks
   g_dev_records.fetch_add(n, std::memory_order_relaxed);
-  std::vector<uint64_t> so, mo, words;
+  std::vector<uint64_t> so, mo, mo2, words;
   for (size_t base = 0; base < n; base += chunk) {
     const size_t m = std::min(chunk, n - base);
     // the byte spans this chunk's records reference, rebased to the upload
@@ -2006,11 +2017,32 @@ int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, 
     };
     uint64_t slo = 0, mlo = 0;
     const size_t sbytes = span(b->sig_off, b->sig_len, so, &slo);
-    const size_t mbytes = span(b->msg_off, b->msg_len, mo, &mlo);
+    size_t mbytes = span(b->msg_off, b->msg_len, mo, &mlo);
+    if (msg2_len) {  // one range over both spans, both offset lists rebased to it
+      uint64_t lo = UINT64_MAX, hi = 0;
+      for (size_t i = base; i < base + m; i++) {
+        if (b->msg_len[i]) {
+          lo = std::min(lo, b->msg_off[i]);
+          hi = std::max(hi, b->msg_off[i] + b->msg_len[i]);
+        }
+        if (msg2_len[i]) {
+          lo = std::min(lo, msg2_off[i]);
+          hi = std::max(hi, msg2_off[i] + msg2_len[i]);
+        }
+      }
+      if (lo == UINT64_MAX) lo = hi = 0;
+      mo2.resize(m);
+      for (size_t i = 0; i < m; i++) {
+        mo[i] = b->msg_len[base + i] ? b->msg_off[base + i] - lo : 0;
+        mo2[i] = msg2_len[base + i] ? msg2_off[base + i] - lo : 0;
+      }
+      mlo = lo;
+      mbytes = (size_t)(hi - lo);
+    }
     if ((sbytes && !b->sig) || (mbytes && !b->msg)) return fail(BH_E_INVALID, "null pointer in batch");
     if (int rc = sync_lanes(d)) return rc;
     HIPCHK(hipStreamSynchronize(s));  // the staging below is reused chunk after chunk
-    const size_t total = round256(m * kb) + 2 * round256(m * 8) + 2 * round256(m * 4) +
+    const size_t total = round256(m * kb) + 3 * round256(m * 8) + 3 * round256(m * 4) +
                          round256(sbytes + 8) + round256(mbytes + 8);
     if (int rc = d.in384.ensure(total)) return rc;
     if (int rc = d.out384.ensure(round256(round64(m) / 8) + round256(m))) return rc;
@@ -2039,10 +2071,18 @@ int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, 
     if (!(q = put(mbytes ? b->msg + mlo : nullptr, mbytes, mbytes + 8)))
       return fail(BH_E_DEVICE, "chunk upload");
     db.msg = (const uint8_t*)q;
+    const uint64_t* dm2o = nullptr;
+    const uint32_t* dm2l = nullptr;
+    if (msg2_len) {
+      if (!(q = put(mo2.data(), m * 8, m * 8))) return fail(BH_E_DEVICE, "chunk upload");
+      dm2o = (const uint64_t*)q;
+      if (!(q = put(msg2_len + base, m * 4, m * 4))) return fail(BH_E_DEVICE, "chunk upload");
+      dm2l = (const uint32_t*)q;
+    }
     uint64_t* dbm = (uint64_t*)d.out384.p;
     uint8_t* drs = (uint8_t*)d.out384.p + round256(round64(m) / 8);
     if (int rc = (flags & kWideHash) ? run_dev_wide(d, curve, &db, m, flags, dbm, drs, s, nullptr)
-                                     : run_dev384(d, &db, m, flags, dbm, drs, s, nullptr))
+                                     : run_dev384(d, &db, m, flags, dbm, drs, s, nullptr, dm2o, dm2l))
       return rc;
     words.resize(round64(m) / 64);
     HIPCHK(hipMemcpyAsync(words.data(), dbm, words.size() * 8, hipMemcpyDeviceToHost, s));
@@ -2565,6 +2605,95 @@ int bh_verify_2seg(int curve, const bh_batch* b, const uint64_t* msg2_off,
   return host_verify(curve, &sb, n, flags, bitmap, reason);
 }
 
+// Records of either NIST curve: the indices split by curve, each group's keys,
+// offsets and lengths gathered (sig / msg stay the caller's buffers), the
+// P-256 group run as bh_verify_2seg / bh_verify run it and the P-384 group
+// through host_verify_chunked, one after the other; reasons and bits scatter
+// back into record order.
+int bh_verify_mixed(const bh_mbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+                    uint8_t* reason) {
+  if (!b) return fail(BH_E_INVALID, "bh_verify_mixed: null batch");
+  if ((b->msg2_off == nullptr) != (b->msg2_len == nullptr))
+    return fail(BH_E_INVALID, "bh_verify_mixed: msg2_off and msg2_len go together (both null: "
+                              "one span)");
+  if (n && (!b->curve || !b->pub || !b->pub_off || !b->sig_off || !b->sig_len || !b->msg_off ||
+            !b->msg_len || !bitmap || !reason))
+    return fail(BH_E_INVALID, "bh_verify_mixed: null pointer in batch");
+  if (int rc = check_flags(flags, "bh_verify_mixed")) return rc;
+  const bool fused = (flags & (BH_F_HASH_SHA256 | BH_F_HASH_SHA3_256)) != 0;
+  if (b->msg2_len && !fused)
+    return fail(BH_E_INVALID, "bh_verify_mixed: second spans are hashed on the device: pass "
+                              "BH_F_HASH_SHA256 or BH_F_HASH_SHA3_256");
+  if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
+  std::vector<uint32_t> idx[2];  // [0]: P-256, [1]: P-384
+  for (size_t i = 0; i < n; i++) {
+    if (b->curve[i] != BH_CURVE_P256 && b->curve[i] != BH_CURVE_P384)
+      return fail(BH_E_INVALID, "bh_verify_mixed: curve[" + std::to_string(i) + "] = " +
+                                    std::to_string((int)b->curve[i]) +
+                                    ": BH_CURVE_P256 or BH_CURVE_P384");
+    idx[b->curve[i] == BH_CURVE_P384].push_back((uint32_t)i);
+  }
+  if (n == 0) return BH_OK;
+  if (all_devs().empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
+  std::memset(bitmap, 0, (n + 7) / 8);
+  std::vector<uint8_t> pub, bm, rs;
+  std::vector<uint64_t> so, mo, mo2;
+  std::vector<uint32_t> sl, ml, ml2;
+  for (int g = 0; g < 2; g++) {
+    const std::vector<uint32_t>& ix = idx[g];
+    const size_t m = ix.size(), kb = g ? 96 : 64;
+    if (!m) continue;
+    pub.resize(m * kb);
+    so.resize(m);
+    sl.resize(m);
+    mo.resize(m);
+    ml.resize(m);
+    for (size_t k = 0; k < m; k++) {
+      const uint32_t i = ix[k];
+      std::memcpy(&pub[k * kb], b->pub + b->pub_off[i], kb);
+      so[k] = b->sig_off[i];
+      sl[k] = b->sig_len[i];
+      mo[k] = b->msg_off[i];
+      ml[k] = b->msg_len[i];
+    }
+    if (b->msg2_len) {
+      mo2.resize(m);
+      ml2.resize(m);
+      for (size_t k = 0; k < m; k++) {
+        mo2[k] = b->msg2_off[ix[k]];
+        ml2[k] = b->msg2_len[ix[k]];
+      }
+    }
+    bm.assign((m + 7) / 8, 0);
+    rs.assign(m, 0);
+    const bh_batch gb{pub.data(), b->sig, so.data(), sl.data(), b->msg, mo.data(), ml.data()};
+    int rc;
+    if (g) {  // BH_F_KEEP_KEYS: ignored for this curve, as in bh_verify
+      rc = host_verify_chunked(BH_CURVE_P384, &gb, m, flags, bm.data(), rs.data(),
+                               b->msg2_len ? mo2.data() : nullptr,
+                               b->msg2_len ? ml2.data() : nullptr);
+    } else if (b->msg2_len) {
+      const SegBatch sb{gb, mo2.data(), ml2.data()};
+      rc = host_verify(BH_CURVE_P256, &sb, m, flags, bm.data(), rs.data());
+    } else {
+      rc = host_verify(BH_CURVE_P256, &gb, m, flags, bm.data(), rs.data());
+    }
+    if (rc) return rc;
+    for (size_t k = 0; k < m; k++) {
+      const uint32_t i = ix[k];
+      reason[i] = rs[k];
+      if ((bm[k >> 3] >> (k & 7)) & 1u) bitmap[i >> 3] |= (uint8_t)(1u << (i & 7));
+    }
+  }
+  return BH_OK;
+}
+
+// Library-internal (fabric.cpp's identity cache; hidden, not part of the C
+// ABI): changes whenever a P-384 key registry has lost its keys.
+extern "C" __attribute__((visibility("hidden"))) uint64_t bhi_keys384_generation() {
+  return g_reg384_gen.load(std::memory_order_relaxed);
+}
+
 int bh_verify_submit(int curve, const bh_batch* b, size_t n, uint32_t flags, uint8_t* bitmap,
                      uint8_t* reason, bh_job** job) {
   if (!job) return fail(BH_E_INVALID, "null job");
@@ -2996,6 +3125,7 @@ int bh_keys384_clear(int device) {
     HIPCHK(hipMemsetAsync(g.count, 0, 4, d.stream));
     HIPCHK(hipStreamSynchronize(d.stream));
     d.reg384_count = 0;
+    g_reg384_gen.fetch_add(1, std::memory_order_relaxed);
     return BH_OK;
   });
 }

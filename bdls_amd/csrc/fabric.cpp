@@ -515,14 +515,15 @@ bool tlv(const uint8_t* b, size_t n, size_t* off, Tlv* t) {
 
 const uint8_t kOidEcPub[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x02, 0x01};
 const uint8_t kOidP256[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x03, 0x01, 0x07};
+const uint8_t kOidP384[] = {0x2b, 0x81, 0x04, 0x00, 0x22};  // secp384r1, 1.3.132.0.34
 const uint8_t kOidEcdsaSha256[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x04, 0x03, 0x02};
 const uint8_t kOidEcdsaSha384[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x04, 0x03, 0x03};
 const uint8_t kOidEcdsaSha512[] = {0x2a, 0x86, 0x48, 0xce, 0x3d, 0x04, 0x03, 0x04};
 
 struct Cert {
   Tlv tbs;               // tbsCertificate (raw = the signed bytes)
-  uint8_t pub[64];       // subject P-256 key X || Y
-  bool p256 = false;
+  uint8_t pub[96];       // subject key X || Y: 64 bytes (P-256) or 96 (P-384)
+  int curve = -1;        // BH_CURVE_P256 / BH_CURVE_P384; -1: any other key (never guessed)
   Tlv sig_alg_oid;       // outer signatureAlgorithm OID
   Tlv sig;               // signatureValue BIT STRING content (after the unused-bits byte)
   bool has_sig = false;
@@ -559,16 +560,25 @@ bool parse_cert(const uint8_t* d, size_t n, Cert* c) {
   Tlv oid1, oid2;
   if (!tlv(algid.p, algid.n, &a, &oid1) || oid1.tag != 0x06) return false;
   if (!tlv(algid.p, algid.n, &a, &oid2)) return false;
-  c->p256 = oid1.n == sizeof(kOidEcPub) && !memcmp(oid1.p, kOidEcPub, sizeof(kOidEcPub)) &&
-            oid2.tag == 0x06 && oid2.n == sizeof(kOidP256) &&
-            !memcmp(oid2.p, kOidP256, sizeof(kOidP256)) && a == algid.n && bits.n == 66 &&
-            bits.p[0] == 0 && bits.p[1] == 0x04;
-  if (c->p256) memcpy(c->pub, bits.p + 2, 64);
+  // id-ecPublicKey with a named curve and the uncompressed point 00 04 X Y of
+  // that curve's size
+  const bool ec = oid1.n == sizeof(kOidEcPub) && !memcmp(oid1.p, kOidEcPub, sizeof(kOidEcPub)) &&
+                  oid2.tag == 0x06 && a == algid.n && bits.n >= 2 && bits.p[0] == 0 &&
+                  bits.p[1] == 0x04;
+  if (ec && oid2.n == sizeof(kOidP256) && !memcmp(oid2.p, kOidP256, sizeof(kOidP256)) &&
+      bits.n == 66) {
+    c->curve = BH_CURVE_P256;
+    memcpy(c->pub, bits.p + 2, 64);
+  } else if (ec && oid2.n == sizeof(kOidP384) && !memcmp(oid2.p, kOidP384, sizeof(kOidP384)) &&
+             bits.n == 98) {
+    c->curve = BH_CURVE_P384;
+    memcpy(c->pub, bits.p + 2, 96);
+  }
   return true;
 }
 
 // ---------------------------------------------------------------- identities
-// SerializedIdentity bytes -> resolved P-256 key + the identity key used by
+// SerializedIdentity bytes -> resolved P-256 or P-384 key + the identity key used by
 // SignatureSetToValidIdentities' de-duplication (Mspid + Id, where Id hashes
 // the SANITIZED certificate: newIdentity, msp/identities.go:55-85 ->
 // sanitizeCert, msp/mspimpl.go:892-935 -> sanitizeECDSASignedCert,
@@ -588,7 +598,8 @@ bool parse_cert(const uint8_t* d, size_t n, Cert* c) {
 // per-signature results).
 struct Ident {
   bool ok = false;
-  uint8_t pub[64];
+  int curve = BH_CURVE_P256;
+  uint8_t pub[96];  // 64 bytes (P-256) or 96 (P-384)
   std::string key;
   uint64_t key_id = 0;  // interned key (IdentCache): equal keys <=> equal ids
 };
@@ -635,9 +646,10 @@ Ident resolve(Span ser) {
   std::vector<uint8_t> der;
   if (!si.id_bytes.set || !pem_decode(si.id_bytes.p, si.id_bytes.n, &der)) return id;
   Cert c;
-  if (!parse_cert(der.data(), der.size(), &c) || !c.p256) return id;
+  if (!parse_cert(der.data(), der.size(), &c) || c.curve < 0) return id;
   id.ok = true;
-  memcpy(id.pub, c.pub, 64);
+  id.curve = c.curve;
+  memcpy(id.pub, c.pub, c.curve == BH_CURVE_P384 ? 96 : 64);
   id.key = dedupe_key(si.mspid, c);
   return id;
 }
@@ -735,15 +747,26 @@ struct SdEntry {
   uint8_t out = BH_SP_NOT_VERIFIED;
 };
 
+struct Batch;
+void offer_keys384(const Batch& b);
+
 // One device batch of signatures (messages hashed on the device). With `base`
 // set (a serialized block), signatures and the one or two message spans of
 // every record index that buffer directly (bh_verify_2seg): no host copy of
 // the signed bytes, and one upload of the block instead of their
 // concatenation. Otherwise pieces are concatenated into `msg` / `sig`.
+// Each record carries its identity's curve; a batch with a P-384 record goes
+// through bh_verify_mixed, in either form, and one without makes the P-256
+// call it always made.
 struct Batch {
   const uint8_t* base = nullptr;
   size_t base_len = 0;
   std::vector<uint8_t> pub, sig, msg;
+  // Only a batch with a P-384 record (any384) keeps these: a P-256 batch pays
+  // nothing for the second curve. Keys lie back to back in pub, 64 or 96 bytes.
+  std::vector<uint8_t> curve;     // per record, from the first P-384 record on (earlier: P-256)
+  std::vector<uint64_t> pub_off;  // per record, made by key_offsets()
+  bool any384 = false;
   std::vector<uint64_t> sig_off, msg_off, msg2_off;
   std::vector<uint32_t> sig_len, msg_len, msg2_len;
   std::vector<uint8_t*> dst;  // where each record's reason goes
@@ -751,8 +774,18 @@ struct Batch {
     return x.n ? (uint64_t)(x.p - base) : 0u;
   }
   bool inside(Span x) const { return !x.n || (x.p >= base && x.p + x.n <= base + base_len); }
-  void add(const uint8_t pub64[64], Span s, const Span* m, int nm, uint8_t* out) {
-    pub.insert(pub.end(), pub64, pub64 + 64);
+  void add(const Ident& id, Span s, const Span* m, int nm, uint8_t* out) {
+    if (__builtin_expect(id.curve == BH_CURVE_P384, 0)) {
+      if (!any384) {
+        curve.assign(dst.size(), (uint8_t)BH_CURVE_P256);
+        any384 = true;
+      }
+      curve.push_back((uint8_t)BH_CURVE_P384);
+      pub.insert(pub.end(), id.pub, id.pub + 96);
+    } else {
+      if (__builtin_expect(any384, 0)) curve.push_back((uint8_t)BH_CURVE_P256);
+      pub.insert(pub.end(), id.pub, id.pub + 64);
+    }
     dst.push_back(out);
     if (base) {  // every span of a block's SignedData lies in the block
       sig_off.push_back(rel(s));
@@ -780,7 +813,7 @@ struct Batch {
     for (int k = 0; k < e.nseg; k++) ok = ok && inside(e.seg[k]);
     return ok;
   }
-  void add(SdEntry& e) { add(e.id->pub, e.sig, e.seg, e.nseg, &e.out); }
+  void add(SdEntry& e) { add(*e.id, e.sig, e.seg, e.nseg, &e.out); }
   void reserve(size_t n, size_t msg_bytes, size_t sig_bytes) {
     pub.reserve(64 * n);
     sig_off.reserve(n);
@@ -797,12 +830,33 @@ struct Batch {
     }
   }
   size_t size() const { return dst.size(); }
+  void key_offsets() {
+    pub_off.resize(curve.size());
+    uint64_t o = 0;
+    for (size_t i = 0; i < curve.size(); i++) {
+      pub_off[i] = o;
+      o += curve[i] == BH_CURVE_P384 ? 96 : 64;
+    }
+  }
   int run(uint32_t flags) {
     const size_t n = size();
     if (!n) return BH_OK;
     std::vector<uint8_t> bitmap((n + 7) / 8), reason(n);
     int rc;
-    if (base) {
+    if (any384) {
+      key_offsets();
+      if (flags & BH_F_KEEP_KEYS) offer_keys384(*this);
+      if (!base) {
+        sig.push_back(0);
+        msg.push_back(0);
+      }
+      const uint8_t* sp = base ? base : sig.data();
+      const uint8_t* mp = base ? base : msg.data();
+      bh_mbatch b{curve.data(), pub.data(), pub_off.data(), sp, sig_off.data(), sig_len.data(),
+                  mp, msg_off.data(), msg_len.data(), base ? msg2_off.data() : nullptr,
+                  base ? msg2_len.data() : nullptr};
+      rc = bh_verify_mixed(&b, n, flags, bitmap.data(), reason.data());
+    } else if (base) {
       bh_batch b{pub.data(), base, sig_off.data(), sig_len.data(),
                  base, msg_off.data(), msg_len.data()};
       rc = bh_verify_2seg(BH_CURVE_P256, &b, msg2_off.data(), msg2_len.data(), n, flags,
@@ -819,6 +873,53 @@ struct Batch {
     return BH_OK;
   }
 };
+
+// BH_FAB_F_KEEP_KEYS for P-384 identities: every record a batch sends to the
+// device under a P-384 key is a sighting of that key; a key at its second
+// sighting (two within one batch count: the coalescer's rule) is offered to
+// the P-384 key registry of every device, once, all keys new in a batch in
+// one registration, before the batch's device work. A full registry leaves
+// the key on the ladder. The offered marks are forgotten when the library
+// reports that a registry lost its keys, so a cleared registry fills again.
+// Results never depend on any of this: the pass gives a registered key's
+// records the same reasons by its table route.
+extern "C" uint64_t bhi_keys384_generation();
+
+struct Keys384Seen {
+  struct Mark {
+    uint32_t sightings = 0;
+    bool offered = false;
+  };
+  std::mutex mu;
+  uint64_t gen = 0;
+  std::unordered_map<std::string, Mark> m;
+  static constexpr size_t kCap = 1 << 16;
+};
+
+void offer_keys384(const Batch& b) {
+  static Keys384Seen* seen = new Keys384Seen();
+  std::lock_guard<std::mutex> g(seen->mu);
+  if (seen->m.size() >= Keys384Seen::kCap) seen->m.clear();
+  if (seen->gen != bhi_keys384_generation())
+    for (auto& kv : seen->m) kv.second.offered = false;
+  std::vector<Keys384Seen::Mark*> due;
+  std::vector<uint8_t> keys;
+  for (size_t i = 0; i < b.curve.size(); i++) {
+    if (b.curve[i] != BH_CURVE_P384) continue;
+    const uint8_t* k = b.pub.data() + b.pub_off[i];
+    Keys384Seen::Mark& mk = seen->m[std::string((const char*)k, 96)];
+    if (mk.sightings < 2) mk.sightings++;
+    if (mk.sightings >= 2 && !mk.offered) {
+      mk.offered = true;  // each key once, whatever the registry answers
+      due.push_back(&mk);
+      keys.insert(keys.end(), k, k + 96);
+    }
+  }
+  if (!due.empty() && bh_keys384_register(-1, keys.data(), due.size(), nullptr) != BH_OK)
+    for (Keys384Seen::Mark* mk : due) mk->offered = false;
+  // read after the registration: a first one allocates the registry
+  seen->gen = bhi_keys384_generation();
+}
 
 struct SetRange {
   size_t first, count;
@@ -1478,7 +1579,7 @@ static int block_preverify(const uint8_t* block, size_t len, uint32_t flags, bh_
   }
   std::vector<SetRange> sets;
   for (TxRec& x : t) {
-    if (x.creator_check) creators.add(x.creator->pub, x.signature, &x.payload, 1, &x.creator_out);
+    if (x.creator_check) creators.add(*x.creator, x.signature, &x.payload, 1, &x.creator_out);
     sets.push_back(SetRange{x.end_first, x.end_count});
   }
   std::vector<uint32_t> valid;

@@ -35,6 +35,10 @@ struct In384 {  // device pointers (include/bdls_hip.h bh_batch, 96-byte keys)
   const uint64_t* msg_off;
   const uint32_t* msg_len;
   uint32_t flags;
+  // msg[msg_off, +msg_len) || msg[msg2_off, +msg2_len) in the fused modes
+  // (digest mode never reads them); nullptr = one span
+  const uint64_t* msg2_off = nullptr;
+  const uint32_t* msg2_len = nullptr;
 };
 
 // Workspace, structure of arrays: word k of record i at base[k * ns + i].
@@ -88,15 +92,18 @@ BH_HD bool key_import384(const uint8_t* q, uint32_t qx[14], uint32_t qy[14]) {
 }
 
 // e = hashToNat(digest) for record i: the leftmost 48 bytes of the given
-// digest (a shorter one whole), or the fused 32-byte hash; one reduction mod n.
+// digest (a shorter one whole), or the fused 32-byte hash of the record's one
+// or two spans; one reduction mod n.
 BH_HD void digest_e384(const In384& in, uint32_t i, uint32_t e[12]) {
   const uint32_t mlen = in.msg_len[i];
+  const uint32_t mlen2 = in.msg2_len ? in.msg2_len[i] : 0u;  // fused modes only
   const uint8_t* m = in.msg + in.msg_off[i];
 #pragma unroll
   for (int k = 0; k < 12; k++) e[k] = 0;
   if (in.flags & F384_HASH_SHA3_256) {
     uint8_t hb[32];
-    sha3_256_msg(hb, m, mlen);
+    if (mlen2) sha3_256_msg2(hb, m, mlen, in.msg + in.msg2_off[i], mlen2);
+    else sha3_256_msg(hb, m, mlen);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const uint8_t* q = hb + 28 - 4 * k;
@@ -104,7 +111,8 @@ BH_HD void digest_e384(const In384& in, uint32_t i, uint32_t e[12]) {
     }
   } else if (in.flags & F384_HASH_SHA256) {
     uint32_t h[8];
-    sha256_msg(h, m, mlen);
+    if (mlen2) sha256_msg2(h, m, mlen, in.msg + in.msg2_off[i], mlen2);
+    else sha256_msg(h, m, mlen);
 #pragma unroll
     for (int k = 0; k < 8; k++) e[k] = h[7 - k];
   } else {

@@ -3,6 +3,9 @@ serialized common.Block whose envelopes are endorser transactions assembled the
 way protoutil.CreateSignedTx assembles them, with real X.509 certificates in
 the SerializedIdentities and P-256 signatures made as bccsp/sw signs
 (ecdsa.Sign + ToLowS, via OpenSSL in libbdlsgen.so). Data preparation only.
+With p384_orgs > 0 the first orgs' CAs, peers and clients hold P-384 keys: the
+CA signs ecdsa-with-SHA384, and the identities sign SHA-256 digests as every
+identity of the MSP does (msp/identities.go:170-227).
 
 Wire layout (fabric-protos-go v0.3.1 field numbers):
   Block{1 header: BlockHeader{1 number, 2 previous_hash, 3 data_hash},
@@ -37,6 +40,7 @@ import numpy as np
 _LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib",
                     "libbdlsgen.so")
 SIG_STRIDE = 80
+SIG_STRIDE_P384 = 112
 
 # ---------------------------------------------------------------- protobuf
 def varint(v: int) -> bytes:
@@ -92,6 +96,9 @@ SEQ = lambda *xs: der(0x30, b"".join(xs))  # noqa: E731
 OID_ECDSA_SHA256 = "1.2.840.10045.4.3.2"
 OID_EC_PUBKEY = "1.2.840.10045.2.1"
 OID_P256 = "1.2.840.10045.3.1.7"
+OID_ECDSA_SHA384 = "1.2.840.10045.4.3.3"
+OID_P384 = "1.3.132.0.34"
+P256, P384 = "P-256", "P-384"
 
 
 def x509_name(org: str, cn: str) -> bytes:
@@ -99,15 +106,18 @@ def x509_name(org: str, cn: str) -> bytes:
                der(0x31, SEQ(der_oid("2.5.4.3"), der(0x0C, cn.encode()))))
 
 
-def x509_tbs(serial: int, issuer: bytes, subject: bytes, pub64: bytes) -> bytes:
-    alg = SEQ(der_oid(OID_ECDSA_SHA256))
+def x509_tbs(serial: int, issuer: bytes, subject: bytes, pub: bytes, curve: str = P256,
+             sig_alg: str = OID_ECDSA_SHA256) -> bytes:
+    """pub: X || Y of the subject key on `curve`; sig_alg: the issuer's."""
+    alg = SEQ(der_oid(sig_alg))
     validity = SEQ(der(0x17, b"250101000000Z"), der(0x17, b"350101000000Z"))
-    spki = SEQ(SEQ(der_oid(OID_EC_PUBKEY), der_oid(OID_P256)), der(0x03, b"\x00\x04" + pub64))
+    spki = SEQ(SEQ(der_oid(OID_EC_PUBKEY), der_oid(OID_P384 if curve == P384 else OID_P256)),
+               der(0x03, b"\x00\x04" + pub))
     return SEQ(der(0xA0, der_int(2)), der_int(serial), alg, issuer, validity, subject, spki)
 
 
-def x509_cert(tbs: bytes, sig_der: bytes) -> bytes:
-    return SEQ(tbs, SEQ(der_oid(OID_ECDSA_SHA256)), der(0x03, b"\x00" + sig_der))
+def x509_cert(tbs: bytes, sig_der: bytes, sig_alg: str = OID_ECDSA_SHA256) -> bytes:
+    return SEQ(tbs, SEQ(der_oid(sig_alg)), der(0x03, b"\x00" + sig_der))
 
 
 def pem(cert: bytes) -> bytes:
@@ -129,10 +139,18 @@ def _gen():
     L.gen_p256_keypair.argtypes = [ctypes.c_uint64, ctypes.c_uint64, vp, vp]
     L.gen_p256_sign_batch.argtypes = [ctypes.c_size_t, vp, vp, ctypes.c_uint64, ctypes.c_int,
                                       vp, vp]
+    L.gen_p384_keypair.argtypes = [ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+    L.gen_p384_sign_batch.argtypes = [ctypes.c_size_t, vp, vp, ctypes.c_int, ctypes.c_uint64,
+                                      ctypes.c_int, vp, vp]
     return L
 
 
-def keypair(L, seed: int, idx: int):
+def keypair(L, seed: int, idx: int, curve: str = P256):
+    if curve == P384:
+        priv = ctypes.create_string_buffer(48)
+        pub = ctypes.create_string_buffer(96)
+        L.gen_p384_keypair(seed, idx, priv, pub)
+        return priv.raw, pub.raw
     priv = ctypes.create_string_buffer(32)
     pub = ctypes.create_string_buffer(64)
     L.gen_p256_keypair(seed, idx, priv, pub)
@@ -141,9 +159,31 @@ def keypair(L, seed: int, idx: int):
 
 def sign_batch(L, privs: list[bytes], digests: list[bytes], seed: int,
                high_s: bool = False) -> list[bytes]:
+    """Record i signs digests[i] with privs[i]: a 32-byte P-256 key or a 48-byte
+    P-384 key (whose digests may be 32 or 48 bytes). The keys of each curve go
+    to the generator as one batch, in order."""
     n = len(privs)
     if n == 0:
         return []
+    wide = [i for i in range(n) if len(privs[i]) == 48]
+    if wide:
+        out: list[bytes] = [b""] * n
+        narrow = [i for i in range(n) if len(privs[i]) != 48]
+        for i, sg in zip(narrow, sign_batch(L, [privs[i] for i in narrow],
+                                            [digests[i] for i in narrow], seed, high_s)):
+            out[i] = sg
+        for dl in sorted({len(digests[i]) for i in wide}):
+            ix = [i for i in wide if len(digests[i]) == dl]
+            pv = np.frombuffer(b"".join(privs[i] for i in ix), np.uint8)
+            dg = np.frombuffer(b"".join(digests[i] for i in ix), np.uint8)
+            buf = np.zeros(len(ix) * SIG_STRIDE_P384, np.uint8)
+            ln = np.zeros(len(ix), np.uint32)
+            rc = L.gen_p384_sign_batch(len(ix), pv.ctypes.data, dg.ctypes.data, dl, seed,
+                                       1 if high_s else 0, buf.ctypes.data, ln.ctypes.data)
+            assert rc == 0
+            for k, i in enumerate(ix):
+                out[i] = buf[k * SIG_STRIDE_P384:k * SIG_STRIDE_P384 + int(ln[k])].tobytes()
+        return out
     pv = np.frombuffer(b"".join(privs), np.uint8)
     dg = np.frombuffer(b"".join(digests), np.uint8)
     out = np.zeros(n * SIG_STRIDE, np.uint8)
@@ -165,34 +205,42 @@ class Identity:
     pub: bytes
     serialized: bytes
     cert_pem: bytes = b""
+    curve: str = P256
 
 
-def make_identities(L, seed: int, norgs: int, nclients: int):
+def make_identities(L, seed: int, norgs: int, nclients: int, p384_orgs: int = 0):
     """One CA per org; one peer (endorser) per org; nclients client identities
-    spread over the orgs. Certificates signed by their org's CA."""
+    spread over the orgs. Certificates signed by their org's CA. The first
+    p384_orgs orgs are P-384 throughout: their CA (which signs
+    ecdsa-with-SHA384), their peer and their clients."""
     cas, peers, clients = [], [], []
+    curve_of = [P384 if o < p384_orgs else P256 for o in range(norgs)]
+    alg_of = [OID_ECDSA_SHA384 if c == P384 else OID_ECDSA_SHA256 for c in curve_of]
     for o in range(norgs):
-        cas.append(keypair(L, seed, 1000 + o))
+        cas.append(keypair(L, seed, 1000 + o, curve_of[o]))
     tbs_list, signer, meta = [], [], []
     for o in range(norgs):
-        priv, pub = keypair(L, seed, 2000 + o)
+        priv, pub = keypair(L, seed, 2000 + o, curve_of[o])
         org = f"Org{o + 1}MSP"
         tbs_list.append(x509_tbs(2000 + o, x509_name(org, f"ca.org{o + 1}"),
-                                 x509_name(org, f"peer0.org{o + 1}"), pub))
+                                 x509_name(org, f"peer0.org{o + 1}"), pub, curve_of[o], alg_of[o]))
         signer.append(cas[o][0])
-        meta.append(("peer", org, priv, pub))
+        meta.append(("peer", o, priv, pub))
     for c in range(nclients):
         o = c % norgs
-        priv, pub = keypair(L, seed, 3000 + c)
+        priv, pub = keypair(L, seed, 3000 + c, curve_of[o])
         org = f"Org{o + 1}MSP"
         tbs_list.append(x509_tbs(3000 + c, x509_name(org, f"ca.org{o + 1}"),
-                                 x509_name(org, f"User{c}@org{o + 1}"), pub))
+                                 x509_name(org, f"User{c}@org{o + 1}"), pub, curve_of[o], alg_of[o]))
         signer.append(cas[o][0])
-        meta.append(("client", org, priv, pub))
-    sigs = sign_batch(L, signer, [hashlib.sha256(t).digest() for t in tbs_list], seed + 77)
-    for tbs, sg, (kind, org, priv, pub) in zip(tbs_list, sigs, meta):
-        cp = pem(x509_cert(tbs, sg))
-        ident = Identity(org, priv, pub, serialized_identity(org, cp), cp)
+        meta.append(("client", o, priv, pub))
+    digests = [(hashlib.sha384 if curve_of[o] == P384 else hashlib.sha256)(t).digest()
+               for t, (_, o, _, _) in zip(tbs_list, meta)]
+    sigs = sign_batch(L, signer, digests, seed + 77)
+    for tbs, sg, (kind, o, priv, pub) in zip(tbs_list, sigs, meta):
+        org = f"Org{o + 1}MSP"
+        cp = pem(x509_cert(tbs, sg, alg_of[o]))
+        ident = Identity(org, priv, pub, serialized_identity(org, cp), cp, curve_of[o])
         (peers if kind == "peer" else clients).append(ident)
     return cas, peers, clients
 
@@ -218,6 +266,9 @@ class FabricBlock:
     tx_valid_identities: list[int] = field(default_factory=list)
     tx_class: list[str] = field(default_factory=list)
     n_signatures: int = 0
+    p384_keys: set = field(default_factory=set)  # (x, y) of every P-384 identity generated
+    identities: list = field(default_factory=list)  # peers, then clients
+    cas: list = field(default_factory=list)  # (priv, pub) per org
 
     @property
     def ntx(self) -> int:
@@ -242,17 +293,22 @@ def _rand_bytes(st, n: int) -> bytes:
 def generate_fabric_block(ntx: int = 500, endorsements: int = 3, norgs: int = 4,
                           nclients: int = 50, corrupt_den: int = 100, seed: int = 3,
                           ext_len: int = 600, ccpp_len: int = 300,
-                          classes: list[str] | None = None) -> FabricBlock:
+                          classes: list[str] | None = None, p384_orgs: int = 0) -> FabricBlock:
     """BASELINE config 3: one block of ntx endorser transactions, each with a
     creator signature and `endorsements` endorsements by distinct org peers.
     1/corrupt_den of the transactions carry one corruption from CORRUPTIONS
-    (or `classes`, cycled, when given: then every tx is corrupted in turn)."""
+    (or `classes`, cycled, when given: then every tx is corrupted in turn).
+    The first p384_orgs orgs hold P-384 keys (make_identities); with 0 the
+    block is what it always was."""
     L = _gen()
     st = [seed * 0x2545F4914F6CDD1D + 11]
-    cas, peers, clients = make_identities(L, seed, norgs, nclients)
+    cas, peers, clients = make_identities(L, seed, norgs, nclients, p384_orgs)
     bad_ident = serialized_identity("Org1MSP", b"-----BEGIN CERTIFICATE-----\nnot base64!\n"
                                                b"-----END CERTIFICATE-----\n")
     fb = FabricBlock(block=b"")
+    fb.identities, fb.cas = peers + clients, cas
+    fb.p384_keys = {(int.from_bytes(i.pub[:48], "big"), int.from_bytes(i.pub[48:], "big"))
+                    for i in fb.identities if i.curve == P384}
     # phase 1: per tx, everything up to the endorsement signatures
     txs = []
     for t in range(ntx):
@@ -390,7 +446,7 @@ BLOCKSIG_CORRUPTIONS = ["none", "sig_flip", "dup_signer", "bad_identity", "high_
 
 
 def generate_signed_blocks(nblocks: int = 16, norderers: int = 4, seed: int = 21,
-                           classes: list[str] | None = None):
+                           classes: list[str] | None = None, p384_orgs: int = 0):
     """Blocks as an orderer cluster delivers them: the SIGNATURES metadata
     entry carries one MetadataSignature per orderer over Metadata.value ||
     signature_header || BlockHeaderBytes(header) (protoutil/blockutils.go
@@ -398,7 +454,7 @@ def generate_signed_blocks(nblocks: int = 16, norderers: int = 4, seed: int = 21
     per-signature BH_R_* / 253 dup / 254 bad identity, valid identities)."""
     L = _gen()
     st = [seed * 0x2545F4914F6CDD1D + 5]
-    _, orderers, _ = make_identities(L, seed, norderers, 0)
+    _, orderers, _ = make_identities(L, seed, norderers, 0, p384_orgs)  # the first ones P-384
     bad_ident = serialized_identity("OrdererMSP", b"-----BEGIN CERTIFICATE-----\n!!\n"
                                                   b"-----END CERTIFICATE-----\n")
     blocks, expected = [], []
@@ -451,7 +507,7 @@ BFT_BLOCKSIG_CORRUPTIONS = ["none", "sig_flip", "unknown_id", "dup_consenter", "
 
 
 def generate_bft_signed_blocks(nblocks: int = 20, norderers: int = 4, seed: int = 31,
-                               classes: list[str] | None = None):
+                               classes: list[str] | None = None, p384_orgs: int = 0):
     """Blocks as a BFT orderer cluster (consensus type "BFT", which this fork
     gives BDLS) signs them: each MetadataSignature has an empty
     signature_header and an IdentifierHeader{identifier: consenter Id, nonce};
@@ -462,7 +518,7 @@ def generate_bft_signed_blocks(nblocks: int = 20, norderers: int = 4, seed: int 
     identities) with 252 for identifiers outside the set."""
     L = _gen()
     st = [seed * 0x2545F4914F6CDD1D + 9]
-    _, orderers, _ = make_identities(L, seed, norderers, 0)
+    _, orderers, _ = make_identities(L, seed, norderers, 0, p384_orgs)  # the first ones P-384
     garbage = b"-----BEGIN CERTIFICATE-----\n!!\n-----END CERTIFICATE-----\n"
     consenters = [(k + 1, o.mspid.encode(), o.cert_pem) for k, o in enumerate(orderers)]
     # first match wins (a later consenter with Id 2 is never consulted); Id 90

@@ -55,9 +55,9 @@ static void rand_scalar(uint64_t *s, BIGNUM *out, const BIGNUM *n, BN_CTX *ctx) 
   } while (BN_is_zero(out));
 }
 
-/* DER INTEGER from a non-negative BIGNUM (minimal) */
+/* DER INTEGER from a non-negative BIGNUM (minimal; up to 384 bits) */
 static size_t der_int(uint8_t *o, const BIGNUM *v, int nonmin, int longlen) {
-  uint8_t mag[40];
+  uint8_t mag[56];
   int L = BN_bn2bin(v, mag);
   size_t k = 0;
   int pad = (L == 0) || (mag[0] & 0x80);
@@ -685,6 +685,93 @@ int gen_p256_sign_batch(size_t n, const uint8_t *priv, const uint8_t *digest, ui
     size_t bl = der_int(body, r, 0, 0);
     bl += der_int(body + bl, s, 0, 0);
     o[0] = 0x30;
+    o[1] = (uint8_t)bl;
+    memcpy(o + 2, body, bl);
+    len[i] = (uint32_t)(bl + 2);
+  }
+  EC_POINT_free(R);
+  BIGNUM *v[] = {nn, half, k, kinv, r, s, e, d, t, x};
+  for (size_t q = 0; q < sizeof(v) / sizeof(v[0]); q++) BN_free(v[q]);
+  BN_CTX_free(ctx);
+  EC_GROUP_free(g);
+  return 0;
+}
+
+/* ---------------------------------------------------------------------------
+ * The same pair on P-384, for the orgs whose CA issues P-384 certificates:
+ * 48-byte private keys, 96-byte public keys X || Y, and signatures over
+ * digests of digest_len bytes -- 32 for an identity's signatures (the MSP
+ * hashes with its 256-bit family whatever the key's curve,
+ * msp/identities.go:170-227), 48 for a CA's ecdsa-with-SHA384 -- taken as
+ * hashToNat takes them (the leftmost 48 bytes). out + 112 i receives the DER
+ * signature. Nonces and keys come from 64 bytes of the stream.
+ * ------------------------------------------------------------------------- */
+#define SIG_STRIDE_P384 112
+
+static void rand_scalar64(uint64_t *s, BIGNUM *out, const BIGNUM *n, BN_CTX *ctx) {
+  uint8_t b[64];
+  do {
+    rand_bytes(s, b, 64);
+    BN_bin2bn(b, 64, out);
+    BN_nnmod(out, out, n, ctx);
+  } while (BN_is_zero(out));
+}
+
+int gen_p384_keypair(uint64_t seed, uint64_t idx, uint8_t *priv48, uint8_t *pub96) {
+  EC_GROUP *g = EC_GROUP_new_by_curve_name(NID_secp384r1);
+  BN_CTX *ctx = BN_CTX_new();
+  BIGNUM *n = BN_new(), *d = BN_new(), *x = BN_new(), *y = BN_new();
+  EC_GROUP_get_order(g, n, ctx);
+  EC_POINT *Q = EC_POINT_new(g);
+  uint64_t st = seed * 0xff51afd7ed558ccdull + idx * 0xc4ceb9fe1a85ec53ull + 0x384;
+  rand_scalar64(&st, d, n, ctx);
+  EC_POINT_mul(g, Q, d, NULL, NULL, ctx);
+  EC_POINT_get_affine_coordinates(g, Q, x, y, ctx);
+  BN_bn2binpad(d, priv48, 48);
+  BN_bn2binpad(x, pub96, 48);
+  BN_bn2binpad(y, pub96 + 48, 48);
+  EC_POINT_free(Q);
+  BN_free(n); BN_free(d); BN_free(x); BN_free(y);
+  BN_CTX_free(ctx);
+  EC_GROUP_free(g);
+  return 0;
+}
+
+int gen_p384_sign_batch(size_t n, const uint8_t *priv, const uint8_t *digest, int digest_len,
+                        uint64_t seed, int high_s, uint8_t *out, uint32_t *len) {
+  if (digest_len <= 0 || digest_len > 64) return -1;
+  EC_GROUP *g = EC_GROUP_new_by_curve_name(NID_secp384r1);
+  BN_CTX *ctx = BN_CTX_new();
+  BIGNUM *nn = BN_new(), *half = BN_new(), *k = BN_new(), *kinv = BN_new(), *r = BN_new(),
+         *s = BN_new(), *e = BN_new(), *d = BN_new(), *t = BN_new(), *x = BN_new();
+  EC_GROUP_get_order(g, nn, ctx);
+  BN_rshift1(half, nn);
+  EC_POINT *R = EC_POINT_new(g);
+  const int take = digest_len < 48 ? digest_len : 48;
+  for (size_t i = 0; i < n; i++) {
+    uint64_t st = seed * 0x100000001b3ull + i * 0x9e3779b97f4a7c15ull + 0x384;
+    BN_bin2bn(priv + 48 * i, 48, d);
+    BN_bin2bn(digest + (size_t)digest_len * i, take, e);
+    BN_nnmod(e, e, nn, ctx);
+    do {
+      rand_scalar64(&st, k, nn, ctx);
+      EC_POINT_mul(g, R, k, NULL, NULL, ctx);
+      EC_POINT_get_affine_coordinates(g, R, x, NULL, ctx);
+      BN_nnmod(r, x, nn, ctx);
+      BN_mod_inverse(kinv, k, nn, ctx);
+      BN_mod_mul(t, r, d, nn, ctx);
+      BN_mod_add(t, t, e, nn, ctx);
+      BN_mod_mul(s, kinv, t, nn, ctx);
+    } while (BN_is_zero(r) || BN_is_zero(s));
+    if (high_s) {
+      if (BN_cmp(s, half) <= 0) BN_sub(s, nn, s);
+    } else if (BN_cmp(s, half) > 0) {
+      BN_sub(s, nn, s);
+    }
+    uint8_t body[SIG_STRIDE_P384], *o = out + (size_t)i * SIG_STRIDE_P384;
+    size_t bl = der_int(body, r, 0, 0);
+    bl += der_int(body + bl, s, 0, 0);
+    o[0] = 0x30; /* at most 2 * (2 + 49) = 102 bytes: the short length form */
     o[1] = (uint8_t)bl;
     memcpy(o + 2, body, bl);
     len[i] = (uint32_t)(bl + 2);

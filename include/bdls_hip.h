@@ -200,6 +200,34 @@ int bh_verify_2seg(int curve, const bh_batch *b, const uint64_t *msg2_off,
                    const uint32_t *msg2_len, size_t n, uint32_t flags, uint8_t *bitmap,
                    uint8_t *reason);
 
+/* A host-memory batch whose records may be of either NIST curve (a Fabric
+ * channel where one org's CA issues P-384 certificates: bccsp/sw/keyimport.go
+ * imports any *ecdsa.PublicKey, and identity.Verify hashes with the MSP's
+ * 256-bit family whatever the key's curve, msp/identities.go:170-227).
+ * Record i is verified under curve[i]; its key is the bh_curve_key_bytes(curve[i])
+ * bytes at pub + pub_off[i]; its message is msg[msg_off[i], +msg_len[i]) ||
+ * msg[msg2_off[i], +msg2_len[i]) (msg2_off and msg2_len both NULL, or
+ * msg2_len[i] = 0: one span; second spans need a fused hash flag).
+ * The result for record i is, bit for bit, what bh_verify gives that record
+ * alone under curve[i] with the same flags (two spans: over the concatenated
+ * message). flags: BH_F_HASH_SHA256, BH_F_HASH_SHA3_256, BH_F_NO_LOW_S and
+ * BH_F_KEEP_KEYS (the P-256 records; ignored for P-384, whose kept tables are
+ * the bh_keys384_* registry's). BH_F_HASH_SHA384 / BH_F_HASH_SHA512 are refused.
+ * The P-256 records run as a bh_verify_2seg / bh_verify batch over all
+ * devices, the P-384 records as a bh_verify batch on the first device;
+ * bh_device_stats counts one batch per non-empty curve group. Every bit of
+ * the ceil(n / 8) bitmap bytes is written (padding bits zero). */
+typedef struct bh_mbatch {
+  const uint8_t  *curve;    /* n: BH_CURVE_P256 or BH_CURVE_P384 per record */
+  const uint8_t  *pub;      /* record i's key at pub + pub_off[i] */
+  const uint64_t *pub_off;
+  const uint8_t  *sig;  const uint64_t *sig_off;  const uint32_t *sig_len;
+  const uint8_t  *msg;  const uint64_t *msg_off;  const uint32_t *msg_len;
+  const uint64_t *msg2_off; const uint32_t *msg2_len;  /* both NULL: one span */
+} bh_mbatch;
+int bh_verify_mixed(const bh_mbatch *b, size_t n, uint32_t flags, uint8_t *bitmap,
+                    uint8_t *reason);
+
 /* Asynchronous form of bh_verify (the pipelined BatchVerify): enqueues the
  * upload (copy stream), the verify passes and the result download (compute
  * stream) on every device and returns at once with *job. bh_verify_wait(job)
@@ -457,9 +485,14 @@ int bh_bdls_preverify(int curve, const uint8_t *msgs, const uint64_t *msg_off,
  *     is checked only while no earlier one of it verified)
  * are verified with identity.Verify semantics (msp/identities.go:170-199:
  * SHA-256, or SHA3-256 with BH_FAB_F_SHA3; Fabric's low-S rule). Identities
- * (msp.SerializedIdentity: PEM X.509) resolve to P-256 keys through a
- * long-lived cache; one this library cannot resolve is reported, never
- * guessed. Checks that do not decide which signatures are verified
+ * (msp.SerializedIdentity: PEM X.509) resolve to P-256 or P-384 keys
+ * (id-ecPublicKey with prime256v1 or secp384r1) through a long-lived cache;
+ * one this library cannot resolve (any other key) is reported, never guessed.
+ * A P-384 identity's signatures are hashed with the same 256-bit family and
+ * verified under its curve: a call that meets one sends its batch through
+ * bh_verify_mixed, and one that meets none makes the P-256 call it always
+ * made. The same holds for the signature-set, envelope and block-signature
+ * entry points below. Checks that do not decide which signatures are verified
  * (CheckTxID, the proposal hash, channel / ledger state, policies) stay with
  * the unchanged validator, which consults the per-signature results.
  *
@@ -470,7 +503,10 @@ int bh_bdls_preverify(int curve, const uint8_t *msgs, const uint64_t *msg_off,
  * BH_FAB_E_DUPLICATE (skipped by the de-duplication), BH_FAB_E_BAD_IDENTITY,
  * or BH_SP_NOT_VERIFIED. */
 #define BH_FAB_F_SHA3 1u      /* the MSPs' SignatureHashFamily is SHA3 */
-#define BH_FAB_F_KEEP_KEYS 2u /* keys used >= 2 times get kept tables (BH_F_KEEP_KEYS) */
+#define BH_FAB_F_KEEP_KEYS 2u /* keys used >= 2 times get kept tables (BH_F_KEEP_KEYS); a
+                                 resolved P-384 key is offered to the bh_keys384_* registry
+                                 of every device at its second sighting, once (a full
+                                 registry leaves it on the ladder; results never differ) */
 #define BH_FAB_F_DECODE_ONLY 4u /* decode, resolve and plan only: no device work, every
                                    signature BH_SP_NOT_VERIFIED (host-side structure checks) */
 
