@@ -11,7 +11,8 @@ HDRS := $(wildcard $(CSRC)/*.h) include/bdls_hip.h
 
 all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so \
      tests/native/build/libhostsim384.so tests/native/build/libhostsim384k.so \
-     tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so $(LIB)/csp_load
+     tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so \
+     tests/native/build/libhostsimfused.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -74,6 +75,11 @@ tests/native/build/libhostsim384s.so: tests/native_p384seg/hostsim384_seg.cpp \
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
 
 tests/native/build/libhostsim512.so: tests/native_sha512/hostsim_sha512.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
+
+# the fused field / point formulas (f_mul2, j_zaddc, the composite 2A + T) on their own
+tests/native/build/libhostsimfused.so: tests/native_fused/hostsim_fused.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
 

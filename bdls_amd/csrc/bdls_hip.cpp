@@ -625,8 +625,12 @@ int env_route() {
 bh::LaunchOpts launch_opts(size_t m, uint32_t flags) {
   bh::LaunchOpts o;
   // records per inversion lane: ~2 waves per SIMD at 1M records (measured
-  // k_inv at 1M: 4 per lane 0.207 ms, 8 0.155, 16 0.159; 2 0.336);
-  // BH_INV_CHUNK overrides for tuning
+  // k_inv at 1M: 4 per lane 0.207 ms, 8 0.155, 16 0.159; 2 0.336). On the
+  // whole config-2 step, three alternating rounds on one box, 32 per lane was
+  // below 8 in every round by about 0.05 ms (5.346 / 5.308 / 5.287 against
+  // 5.417 / 5.354 / 5.338 ms), less than the 0.079 ms the default's own runs
+  // drifted over the call: the rule is kept and the question left open
+  // (DESIGN 4.11). BH_INV_CHUNK overrides for tuning
   static const long env_chunk = [] {
     const char* e = getenv("BH_INV_CHUNK");
     return e ? atol(e) : 0L;

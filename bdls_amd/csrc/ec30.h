@@ -186,17 +186,62 @@ BH_HD bool j_degenerate(const uint32_t z3[9], const uint32_t rr[9], bool* same_y
   return degenerate;
 }
 
+// Co-Z addition WITHOUT the partner update: the second half of the composite
+// 2 p + q = (p + q) + p. An addition s = p + q leaves p rescaled onto s's Z as
+// intermediates, P1 = (x1, y1, z) = (V, Y1 H^3, Z3), and s itself is
+// P2 = (x2, sy - y1, z) with x2 = X3 and sy = r (V - X3), whose y is never
+// formed: the co-Z addition with P1 in the first role (ZADDU's p) needs
+//   X1 - X2 = V - X3 = dx, which the addition has already formed,
+//   Y1 - Y2 = 2 y1 - sy, one pass from the two products (f_dblsub),
+// and its Y3 = (Y1 - Y2)(W1 - X3) + Y1 (W2 - W1) is one f_mul2 on P-256. No
+// A1 product and no copies: nothing reads the rescaled partner afterwards.
+// Requires beta(x1), beta(y1), beta(sy), beta(z) <= 2, beta(x2) <= 34,
+// beta(dx) <= 40; r aliases none of the inputs. Output beta (34, 2, 2) on
+// P-256; (34, 34, 2) with two products, which secp256k1 (see f_mul2) and
+// FUSE = false take. FUSE = false is the ladder's composite (j_add_da): there
+// the four operands of f_mul2 and the columns live beside the ladder's state,
+// and k_ktab_ladder needed 256 VGPRs + 22 AGPRs (1 wave per SIMD by the
+// compiler's count, against 2): the build kernel +21 % cycles at config 2
+// (DESIGN 4.11). Incomplete as j_zaddu: Z3 = z dx is 0 mod p iff P1 == +-P2,
+// which callers test.
+template <class F, bool FUSE = true>
+BH_HD void j_zaddc(J30& r, const uint32_t x1[9], const uint32_t y1[9], const uint32_t x2[9],
+                   const uint32_t dx[9], const uint32_t sy[9], const uint32_t z[9]) {
+  uint32_t c[9], w1[9], w2[9], t2[9], d[9], t3[9], t4[9];
+  f_sqr<F>(c, dx);                        // [b2]   C = (X1 - X2)^2: 1600
+  f_mul<F>(w1, x1, c);                    // [b2]   W1 = X1 C
+  f_mul<F>(w2, x2, c);                    // [b2]   W2 = X2 C: 34*2
+  f_dblsub<F, 32>(t2, y1, sy);            // [b36]  Y1 - Y2 = 2 y1 - sy
+  f_sqr<F>(d, t2);                        // [b2]   D = (Y1 - Y2)^2: 1296
+  f_sub2<F, 32>(r.X, d, w1, w2);          // [b34]  X3 = D - W1 - W2 (one pass)
+  f_sub<F, 64>(t3, w1, r.X);              // [b66]
+  if constexpr (F::sparse_p256 && FUSE) {
+    f_sub<F, 32>(t4, w2, w1);             // [b34]  -(W1 - W2)
+    f_mul2<F>(r.Y, t2, t3, y1, t4);       // [b2]   36*66 + 2*34 = 2444
+  } else {
+    f_sub<F, 32>(t4, w1, w2);             // [b34]
+    f_mul<F>(t4, y1, t4);                 // [b2]   A1 = Y1 (W1 - W2)
+    f_mul<F>(t3, t2, t3);                 // [b2]   36*66
+    f_sub<F, 32>(r.Y, t3, t4);            // [b34]
+  }
+  f_mul<F>(r.Z, z, dx);                   // [b2]   Z3 = Z (X1 - X2): 2*40
+}
+
 // r = p + (+-q) (Jacobian, neither at infinity; neg adds -q: q's sign folded
-// into r = S2 - S1, f_csub). With CO, pz = p rescaled to r's Z, (U1 H^2,
-// S1 H^3, Z3) -- both intermediates of the addition, the co-Z partner j_zaddu
-// needs for 2 p + q = (p + q) + p. Requires beta <= 63 on X1, Y1, X2, Y2 and
-// beta <= 34 on Z1, Z2 (products below stay <= 16000). Output beta (34, 34,
-// 2), pz (2, 2, 2). Returns true iff x(p) == x(q) (degenerate); then r is
-// garbage and *same_y says p == +-q (double) vs p == -(+-q) (infinity). r may
-// alias p. Round 6: H^3 + 2V once (f_add2x), X3 and V - X3 from it in one
-// pass each (was five passes), the sign in the r pass (was a negation + select).
-template <class F, bool CO>
-BH_HD bool j_add_impl(J30& r, J30* pz, const J30& p, const J30& q, bool neg, bool* same_y) {
+// into r = S2 - S1, f_csub). With DA, r = 2 p + (+-q) as (p + q) + p: p
+// rescaled to the sum's Z, (U1 H^2, S1 H^3, Z3), is made of intermediates of
+// the addition, and j_zaddc adds it to the sum. Requires beta <= 63 on X1, Y1,
+// X2, Y2 and beta <= 34 on Z1, Z2 (products below stay <= 16000). Output beta
+// (34, 2, 2) on P-256 (Y3 = r (V - X3) + (32 p - S1) H^3 as one f_mul2);
+// (34, 34, 2) on secp256k1 and with DA (j_zaddc with two products).
+// Returns true iff x(p) == x(q) (degenerate);
+// *same_y then says p == +-q (double) vs p == -(+-q) (infinity), and r is
+// garbage without DA and NOT WRITTEN with DA (the caller's A == -T case keeps
+// A). r may alias p. Round 6: H^3 + 2V once (f_add2x), X3 and V - X3 from it in
+// one pass each (was five passes), the sign in the r pass (was a negation +
+// select).
+template <class F, bool DA>
+BH_HD bool j_add_impl(J30& r, const J30& p, const J30& q, bool neg, bool* same_y) {
   uint32_t z1z1[9], z2z2[9], u1[9], u2[9], s1[9], s2[9], h[9], rr[9], t[9], hh[9], hhh[9], w[9];
   f_sqr<F>(z1z1, p.Z);                    // [b2]
   f_sqr<F>(z2z2, q.Z);                    // [b2]
@@ -213,39 +258,55 @@ BH_HD bool j_add_impl(J30& r, J30* pz, const J30& p, const J30& q, bool neg, boo
   f_mul<F>(u1, u1, hh);                   // [b2]  V = U1 H^2
   f_sqr<F>(t, rr);                        // [b2]  r^2
   f_add2x(w, hhh, u1);                    // [b6]  H^3 + 2V
-  f_sub<F, 32>(r.X, t, w);                // [b34] X3 = r^2 - H^3 - 2V
-  f_addsub<F, 32>(u2, w, u1, t);          // [b40] V - X3 = 3V + H^3 - r^2
-  f_mul<F>(u2, rr, u2);                   // [b2]  34*40
-  f_mul<F>(s1, s1, hhh);                  // [b2]  S1 H^3
-  f_sub<F, 32>(r.Y, u2, s1);              // [b34] Y3 = r (V - X3) - S1 H^3
-  f_mul<F>(t, p.Z, q.Z);                  // [b2]
-  f_mul<F>(r.Z, t, h);                    // [b2]  Z3 = Z1 Z2 H
-  if constexpr (CO) {
-    f_copy(pz->X, u1);
-    f_copy(pz->Y, s1);
-    f_copy(pz->Z, r.Z);
+  if constexpr (DA) {
+    uint32_t x3[9], z3[9];
+    f_sub<F, 32>(x3, t, w);               // [b34] X3 = r^2 - H^3 - 2V
+    f_addsub<F, 32>(u2, w, u1, t);        // [b40] V - X3 = 3V + H^3 - r^2
+    f_mul<F>(s2, rr, u2);                 // [b2]  r (V - X3): 34*40
+    f_mul<F>(s1, s1, hhh);                // [b2]  S1 H^3
+    f_mul<F>(t, p.Z, q.Z);                // [b2]
+    f_mul<F>(z3, t, h);                   // [b2]  Z3 = Z1 Z2 H
+    if (j_degenerate<F>(z3, rr, same_y)) return true;
+    j_zaddc<F, false>(r, u1, s1, x3, u2, s2, z3);  // two products: see j_zaddc
+    return false;
+  } else {
+    f_sub<F, 32>(r.X, t, w);              // [b34] X3 = r^2 - H^3 - 2V
+    f_addsub<F, 32>(u2, w, u1, t);        // [b40] V - X3 = 3V + H^3 - r^2
+    if constexpr (F::sparse_p256) {
+      f_neg<F, 32>(s2, s1);               // [b33] 32 p - S1
+      f_mul2<F>(r.Y, rr, u2, s2, hhh);    // [b2]  Y3 = r (V - X3) - S1 H^3: 34*40 + 33*2 = 1426
+    } else {
+      f_mul<F>(u2, rr, u2);               // [b2]  34*40
+      f_mul<F>(s1, s1, hhh);              // [b2]  S1 H^3
+      f_sub<F, 32>(r.Y, u2, s1);          // [b34] Y3 = r (V - X3) - S1 H^3
+    }
+    f_mul<F>(t, p.Z, q.Z);                // [b2]
+    f_mul<F>(r.Z, t, h);                  // [b2]  Z3 = Z1 Z2 H
+    return j_degenerate<F>(r.Z, rr, same_y);
   }
-  return j_degenerate<F>(r.Z, rr, same_y);
 }
 
 template <class F>
 BH_HD bool j_add(J30& r, const J30& p, const J30& q, bool* same_y) {
-  return j_add_impl<F, false>(r, nullptr, p, q, false, same_y);
+  return j_add_impl<F, false>(r, p, q, false, same_y);
 }
+// r = 2 p + (+-q); on a degenerate p + q (true) r is not written
 template <class F>
-BH_HD bool j_add_co(J30& r, J30& pz, const J30& p, const J30& q, bool* same_y, bool neg = false) {
-  return j_add_impl<F, true>(r, &pz, p, q, neg, same_y);
+BH_HD bool j_add_da(J30& r, const J30& p, const J30& q, bool* same_y, bool neg = false) {
+  return j_add_impl<F, true>(r, p, q, neg, same_y);
 }
 
 // r = p + (x2, +-y2, 1) (mixed; neg adds (x2, -y2)). Requires beta <= 63 on X1
 // and beta <= 94 on Y1 (the sign pass needs S2 + Y1 <= 96 p; a point whose y
 // was negated by f_neg<64> has beta 64), beta(Z1) <= 34, beta(x2),
-// beta(y2) <= 64. Output beta (34, 34, 2); with CO, pz = (X1 H^2, Y1 H^3, Z3) beta
-// (2, 2, 2) (j_madd_co: the composite 2 p + q = (p + q) + p). Degenerate
-// contract as j_add_impl; r may alias p.
-template <class F, bool CO>
-BH_HD bool j_madd_impl(J30& r, J30* pz, const J30& p, const uint32_t x2[9], const uint32_t y2[9],
-                       bool neg, bool* same_y) {
+// beta(y2) <= 64. Output beta (34, 2, 2) on P-256 (Y3 = r (V - X3) +
+// (96 p - Y1) H^3 as one f_mul2; Y1 is negated as it stands, up to 94 p) and
+// (34, 34, 2) on secp256k1. With DA, r = 2 p + (+-q) as (p + q) + p through
+// j_zaddc, p rescaled as (X1 H^2, Y1 H^3, Z3) (j_madd_da). Degenerate contract
+// as j_add_impl; r may alias p.
+template <class F, bool DA>
+BH_HD bool j_madd_impl(J30& r, const J30& p, const uint32_t x2[9], const uint32_t y2[9], bool neg,
+                       bool* same_y) {
   uint32_t z1z1[9], u2[9], s2[9], h[9], rr[9], t[9], hh[9], hhh[9], v[9], w[9];
   f_sqr<F>(z1z1, p.Z);                    // [b2]
   f_mul<F>(u2, x2, z1z1);                 // [b2]
@@ -259,29 +320,42 @@ BH_HD bool j_madd_impl(J30& r, J30* pz, const J30& p, const uint32_t x2[9], cons
   f_mul<F>(v, p.X, hh);                   // [b2]  V = X1 H^2
   f_sqr<F>(t, rr);                        // [b2]  9604
   f_add2x(w, hhh, v);                     // [b6]  H^3 + 2V
-  f_sub<F, 32>(r.X, t, w);                // [b34] X3 = r^2 - H^3 - 2V
-  f_addsub<F, 32>(s2, w, v, t);           // [b40] V - X3
-  f_mul<F>(s2, rr, s2);                   // [b2]  98*40
-  f_mul<F>(t, p.Y, hhh);                  // [b2]  Y1 H^3
-  f_sub<F, 32>(r.Y, s2, t);               // [b34]
-  f_mul<F>(r.Z, p.Z, h);                  // [b2]  34*66
-  if constexpr (CO) {
-    f_copy(pz->X, v);
-    f_copy(pz->Y, t);
-    f_copy(pz->Z, r.Z);
+  if constexpr (DA) {
+    uint32_t x3[9], z3[9];
+    f_sub<F, 32>(x3, t, w);               // [b34] X3 = r^2 - H^3 - 2V
+    f_addsub<F, 32>(u2, w, v, t);         // [b40] V - X3
+    f_mul<F>(s2, rr, u2);                 // [b2]  r (V - X3): 98*40
+    f_mul<F>(t, p.Y, hhh);                // [b2]  Y1 H^3
+    f_mul<F>(z3, p.Z, h);                 // [b2]  34*66
+    if (j_degenerate<F>(z3, rr, same_y)) return true;
+    j_zaddc<F>(r, v, t, x3, u2, s2, z3);
+    return false;
+  } else {
+    f_sub<F, 32>(r.X, t, w);              // [b34] X3 = r^2 - H^3 - 2V
+    f_addsub<F, 32>(s2, w, v, t);         // [b40] V - X3
+    if constexpr (F::sparse_p256) {
+      f_negk<F, 96>(u2, p.Y);             // [b97] 96 p - Y1 (Y1 <= 94 p)
+      f_mul2<F>(r.Y, rr, s2, u2, hhh);    // [b2]  Y3 = r (V - X3) - Y1 H^3: 98*40 + 97*2 = 4114
+    } else {
+      f_mul<F>(s2, rr, s2);               // [b2]  98*40
+      f_mul<F>(t, p.Y, hhh);              // [b2]  Y1 H^3
+      f_sub<F, 32>(r.Y, s2, t);           // [b34]
+    }
+    f_mul<F>(r.Z, p.Z, h);                // [b2]  34*66
+    return j_degenerate<F>(r.Z, rr, same_y);
   }
-  return j_degenerate<F>(r.Z, rr, same_y);
 }
 
 template <class F>
 BH_HD bool j_madd(J30& r, const J30& p, const uint32_t x2[9], const uint32_t y2[9], bool* same_y,
                   bool neg = false) {
-  return j_madd_impl<F, false>(r, nullptr, p, x2, y2, neg, same_y);
+  return j_madd_impl<F, false>(r, p, x2, y2, neg, same_y);
 }
+// r = 2 p + (x2, +-y2, 1); on a degenerate p + q (true) r is not written
 template <class F>
-BH_HD bool j_madd_co(J30& r, J30& pz, const J30& p, const uint32_t x2[9], const uint32_t y2[9],
+BH_HD bool j_madd_da(J30& r, const J30& p, const uint32_t x2[9], const uint32_t y2[9],
                      bool* same_y, bool neg = false) {
-  return j_madd_impl<F, true>(r, &pz, p, x2, y2, neg, same_y);
+  return j_madd_impl<F, true>(r, p, x2, y2, neg, same_y);
 }
 
 // y^2 == x^3 + a x + b for Montgomery-domain x, y with beta <= 2.

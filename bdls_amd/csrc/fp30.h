@@ -13,6 +13,9 @@
 // whose limbs 0..7 are < 2^30 ("normalised"; limb 8 holds the rest).
 //   f_mul(a, b)  requires beta_a * beta_b <= 16000 and normalised limbs;
 //                returns beta 2 (t < ab/R + p < 2p).
+//   f_mul2(a, b, c, d) = (ab + cd)/R with one reduction: requires
+//                beta_a * beta_b + beta_c * beta_d <= 16000; returns beta 2
+//                (P-256 only)
 //   f_add        beta_a + beta_b
 //   f_sub<K>     a - b + K p, K in {32, 64}: requires beta_b <= K - 1;
 //                returns beta_a + K
@@ -185,6 +188,54 @@ BH_HD void f_add(uint32_t r[9], const uint32_t a[9], const uint32_t b[9]) {
   r[8] = a[8] + b[8] + c;
 }
 
+// t = (a b + c d) / 2^270 mod p with ONE reduction (lazy, beta 2, normalised):
+// the Y3 of the additions, r (V - X3) + (K p - S1) H^3, as one f_redc instead
+// of two products, two reductions and a subtraction pass. Requires normalised
+// limbs and beta_a beta_b + beta_c beta_d <= 16000 (so every beta < 2^14 and
+// limb 8 < 2^30: each limb product is < 2^60).
+// P-256 (sparse f_redc): after a b the columns that hold more than four
+// products (4..12: 5..9 of them, < 9 x 2^60) are partially folded -- column k
+// keeps its low word and 4 x its high word goes to column k + 1, exact because
+// 2^32 at column k is 4 x 2^30. The high words are all read before any column
+// is written, so the nine mads are independent (no serial chain). Each high
+// word is < 9 x 2^28, so a folded column holds < 2^32 + 9 x 2^30 < 2^34, and
+// after c d every column holds <= 9 products + 2^34 (columns 0..3 and 14..16
+// hold <= 4 + 4 products and no fold term, column 13 4 + 4 and a fold term).
+// f_redc's column bound becomes <= 9 products + m p[7] < 2^62 + 2^48 + 2^44 +
+// 2^38 + its own carry 13.01 x 2^30 < 2^34 + the fold term 2^34
+//   < (9 + 4) 2^60 + 2^49 < 13.01 x 2^60 (0.01 x 2^60 > 2^53),
+// the same bound as a single product's, so f_redc is unchanged, and its output
+// bound t < (a b + c d)/R + (1 + 2^-28) p < (16000/16384 + 1 + 2^-28) p < 2p.
+// P-256 only (static_assert): on secp256k1's generic f_redc a column also
+// takes up to eight m_j p[k-j] < 2^60, and 9 + 8 terms already lean on limb 8
+// being small, with no room stated for a further term; its formulas keep two
+// products.
+template <class F>
+BH_HD void f_mul2(uint32_t r[9], const uint32_t a[9], const uint32_t b[9], const uint32_t c[9],
+                  const uint32_t d[9]) {
+  static_assert(F::sparse_p256, "f_mul2: the column bound is proved for the sparse P-256 f_redc only");
+  uint64_t C[17];
+#pragma unroll
+  for (int k = 0; k < 17; k++) C[k] = 0;
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+#pragma unroll
+    for (int j = 0; j < 9; j++) C[i + j] += (uint64_t)a[i] * b[j];
+  uint32_t hi[9];
+#pragma unroll
+  for (int k = 4; k <= 12; k++) {
+    hi[k - 4] = (uint32_t)(C[k] >> 32);
+    C[k] = (uint32_t)C[k];
+  }
+#pragma unroll
+  for (int k = 4; k <= 12; k++) mac_k<4u>(C[k + 1], hi[k - 4]);
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+#pragma unroll
+    for (int j = 0; j < 9; j++) C[i + j] += (uint64_t)c[i] * d[j];
+  f_redc<F>(r, C);
+}
+
 // r = a - b + K p (K = 32 or 64), limbs re-normalised. Every limb of the
 // borrowed K p exceeds the matching limb of b, so no intermediate goes negative.
 template <class F, int K>
@@ -296,6 +347,42 @@ BH_HD void f_csub(uint32_t r[9], bool neg, const uint32_t s[9], const uint32_t y
   }
   const uint32_t x8 = neg ? 0u - s[8] : s[8];
   r[8] = kk.v[8] + x8 + cy - y[8];
+}
+
+// r = K p - a for a K beyond f_neg's 32 / 64 (K = 96: a point's Y1 that is a
+// negated table y), from the B = 1 borrowed K p:
+// every limb below the top is >= 2^30 - 1 >= a_i. Requires value(a) <= K p;
+// returns a value <= K p (beta K + 1), normalised. The operand negation that
+// f_mul2 takes in place of the subtraction after the products.
+template <class F, int K>
+BH_HD void f_negk(uint32_t r[9], const uint32_t a[9]) {
+  constexpr Limbs9 kk = KpB<F, K, 1>::k;
+  uint32_t cy = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t t = kk.v[i] + cy - a[i];
+    r[i] = t & kM30;
+    cy = t >> 30;
+  }
+  r[8] = kk.v[8] + cy - a[8];
+}
+
+// r = 2 a - b + K p (K = 32 or 64) in one pass: 2 a_i + kk_i + carry <=
+// 2 (2^30 - 1) + (2^31 - 1) + 3 < 2^32 and kk_i >= b_i (B = 1 borrowed limbs).
+// Requires value(b) <= K p; returns 2 beta_a + K.
+template <class F, int K>
+BH_HD void f_dblsub(uint32_t r[9], const uint32_t a[9], const uint32_t b[9]) {
+  static_assert(K == 32 || K == 64, "K");
+  uint32_t cy = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t kk = (K == 32) ? F::k32[i] : F::k64[i];
+    const uint32_t t = (a[i] << 1) + kk + cy - b[i];
+    r[i] = t & kM30;
+    cy = t >> 30;
+  }
+  const uint32_t k8 = (K == 32) ? F::k32[8] : F::k64[8];
+  r[8] = (a[8] << 1) + k8 + cy - b[8];
 }
 
 // r = K p - a

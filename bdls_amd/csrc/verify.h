@@ -1877,9 +1877,10 @@ BH_HD void ll_madd(J30& A, bool& a_inf, const uint32_t tx[9], uint32_t ty[9], bo
   }
 }
 
-// A = 2 A + T (T = +-(tx, ty)) as (A + T) + A: a mixed addition that also
-// rescales A onto the sum's Z (j_madd_co), then a co-Z addition (j_zaddu):
-// 8M + 3S + 5M + 2S = 18 F_p ops against a doubling + a mixed addition's 19
+// A = 2 A + T (T = +-(tx, ty)) as (A + T) + A (j_madd_da): a mixed addition
+// whose intermediates are A on the sum's Z, then a co-Z addition that does not
+// update its partner (j_zaddc): 8M + 3S + 5M + 2S with the last two products
+// sharing one reduction on P-256, against a doubling + a mixed addition's 19
 // (round 5). Degenerate cases, as branches the lanes skip together: A at
 // infinity -> T; A == T -> 3 T = 2 T + T; A == -T -> A; A + T == -A (the
 // co-Z sum's x difference is 0; A + T == A would need T = 0) -> infinity.
@@ -1896,9 +1897,8 @@ BH_HD void ll_dbladd(J30& A, bool& a_inf, const uint32_t tx[9], uint32_t ty[9], 
     a_inf = false;
     return;
   }
-  J30 R, Az;
   bool same;
-  if (j_madd_co<P>(R, Az, A, tx, ty, &same, neg)) {  // rare: A == +-T
+  if (j_madd_da<P>(A, A, tx, ty, &same, neg)) {  // rare: A == +-T (A not written)
     if (neg) f_neg<P, 64>(ty, ty);
     J30 T;
     f_copy(T.X, tx);
@@ -1910,7 +1910,6 @@ BH_HD void ll_dbladd(J30& A, bool& a_inf, const uint32_t tx[9], uint32_t ty[9], 
     }  // else A == -T: 2 A + T = A, unchanged
     return;
   }
-  j_zaddu<P>(A, R, Az);
   if (f_is_zero2<P>(A.Z)) a_inf = true;  // rare: A + T == -A
 }
 
@@ -1972,7 +1971,7 @@ BH_HD bool stage_keycomb_fold(const Work& w, uint32_t i, const uint32_t* tab, ui
 // when u2 is even, is odd; digit i = 2 b_i - 31 with b_i = bits [5i+1, 5i+5]
 // of k (odd, nonzero, in [-31, 31]), the top digit (i = 51) 2 bit_256 + 1 > 0
 // -- so every window is A = 32 A + d_i Q = 2 (16 A) + d_i Q: 4 doublings and
-// the composite (A + T) + A (j_dbladd: j_add_co + j_zaddu, 16 + 7 F_p ops
+// the composite (A + T) + A (j_dbladd: j_add_da = j_add + j_zaddc, 16 + 7 F_p ops
 // against a doubling's 8 + an addition's 16) with no zero digit to skip. The
 // table holds the odd multiples Q, 3 Q, ..., 31 Q from a co-Z chain (DBLU + 15
 // ZADDU: 114 F_p ops against 162 for 1..16 Q). u1 G is folded into the same
@@ -1997,9 +1996,8 @@ BH_HD void j_dbladd(J30& A, bool& a_inf, J30& T, bool neg) {
     a_inf = false;
     return;
   }
-  J30 R, Az;
   bool same;
-  if (j_add_co<P>(R, Az, A, T, &same, neg)) {  // rare: A == +-T (the sign in its r pass)
+  if (j_add_da<P>(A, A, T, &same, neg)) {  // rare: A == +-T (the sign in its r pass; A not written)
     if (neg) f_neg<P, 64>(T.Y, T.Y);
     if (same) {
       J30 D;
@@ -2008,7 +2006,6 @@ BH_HD void j_dbladd(J30& A, bool& a_inf, J30& T, bool neg) {
     }  // else A == -T: 2 A + T = A, unchanged
     return;
   }
-  j_zaddu<P>(A, R, Az);
   if (f_is_zero2<P>(A.Z)) a_inf = true;  // rare: A + T == -A
 }
 
