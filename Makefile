@@ -12,7 +12,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/bdls_hip.h
 all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so \
      tests/native/build/libhostsim384.so tests/native/build/libhostsim384k.so \
      tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so \
-     tests/native/build/libhostsimfused.so $(LIB)/csp_load
+     tests/native/build/libhostsimfused.so tests/native/build/libhostsim384c.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -74,6 +74,12 @@ tests/native/build/libhostsim384s.so: tests/native_p384seg/hostsim384_seg.cpp \
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
 
+# (hostsim384_comb.cpp includes hostsim384.cpp and adds the per-pass key combs' entries)
+tests/native/build/libhostsim384c.so: tests/native_p384comb/hostsim384_comb.cpp \
+                                      tests/native/hostsim384.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
+
 tests/native/build/libhostsim512.so: tests/native_sha512/hostsim_sha512.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
@@ -88,6 +94,14 @@ tests/native/build/sha512_selftest: tests/native_sha512/sha512_selftest.cpp $(HD
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	  -o $@ $< -lcrypto
+
+# stand-alone sanitizer run of comb384.h on the CPU (tests/test_p384_comb_cpu.py builds and runs it)
+tests/native/build/comb384_selftest: tests/native_p384comb/comb384_selftest.cpp \
+                                     tests/native_p384comb/hostsim384_comb.cpp \
+                                     tests/native/hostsim384.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -o $@ $< -lcrypto -lpthread
 
 # build-kernel experiments (profiles/r02/exp_build): not part of `all`
 EXP_VARIANTS := base:

@@ -21,6 +21,7 @@ BH_F_HASH_SHA3_256 = 8
 BH_F_ANY_LANE = 16
 BH_F_HASH_SHA384 = 32
 BH_F_HASH_SHA512 = 64
+BH_F_BATCH_KEYS = 128
 BH_CURVE_P256 = 0
 BH_CURVE_SECP256K1 = 1
 BH_CURVE_P384 = 2

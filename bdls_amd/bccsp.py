@@ -25,8 +25,8 @@ from typing import Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (BH_F_HASH_SHA256, BH_F_HASH_SHA3_256, BH_F_HASH_SHA384, BH_F_HASH_SHA512,
-                   BH_F_NO_LOW_S, BhBatch)
+from ._lib import (BH_F_BATCH_KEYS, BH_F_HASH_SHA256, BH_F_HASH_SHA3_256, BH_F_HASH_SHA384,
+                   BH_F_HASH_SHA512, BH_F_NO_LOW_S, BhBatch)
 
 # reason codes (include/bdls_hip.h)
 R_OK, R_EMPTY_SIG, R_EMPTY_DIGEST, R_DER, R_R_NONPOS, R_S_NONPOS, R_HIGH_S = range(7)
@@ -198,9 +198,17 @@ def verify_mixed(curve, pub, pub_off, sig, sig_off, sig_len, msg, msg_off, msg_l
 class HipCSP:
     """The `bccsp/hip` provider's verify/hash surface (embeds sw semantics)."""
 
-    def __init__(self, device_mask: int = 0, low_s: bool = True):
+    def __init__(self, device_mask: int = 0, low_s: bool = True, batch_keys: bool = False):
+        """batch_keys: P-384 batch calls set BH_F_BATCH_KEYS, so a key that a pass
+        sees at least 4 times gets a comb table for that pass (results are the
+        same either way; P-256 batches find their repeated keys unasked)."""
         self._flags = 0 if low_s else BH_F_NO_LOW_S
+        self._batch_keys = bool(batch_keys)
         _lib.ensure_init(device_mask)
+
+    def _batch_flags(self, curve: int) -> int:
+        keys = getattr(self, "_batch_keys", False) and curve == _lib.BH_CURVE_P384
+        return self._flags | (BH_F_BATCH_KEYS if keys else 0)
 
     # -- BCCSP.Hash (bccsp/sw/hash.go:29-33). Single-message hashing stays on the
     # host like sw; batched hashing is fused into BatchIdentityVerify on device.
@@ -248,8 +256,9 @@ class HipCSP:
     def batch_verify(self, keys: Sequence[ECDSAPublicKey], signatures: Sequence[bytes],
                      digests: Sequence[bytes]):
         """Returns (valid bool[n], reason u8[n]); reason in ERROR_REASONS <=> Go error."""
-        return verify_packed(*pack_records(keys, signatures, digests), flags=self._flags,
-                             curve=batch_curve(keys))
+        curve = batch_curve(keys)
+        return verify_packed(*pack_records(keys, signatures, digests),
+                             flags=self._batch_flags(curve), curve=curve)
 
     def batch_identity_verify(self, keys: Sequence[ECDSAPublicKey], messages: Sequence[bytes],
                               signatures: Sequence[bytes], family: str = "SHA2",
@@ -261,8 +270,9 @@ class HipCSP:
         (bccsp/sw/conf.go:43-46); SHA-384 and SHA-512 run as a digest pass ahead
         of the curve's pass."""
         flag = hash_flag(hash) if hash is not None else family_flag(family)
+        curve = batch_curve(keys)
         return verify_packed(*pack_records(keys, signatures, messages),
-                             flags=self._flags | flag, curve=batch_curve(keys))
+                             flags=self._batch_flags(curve) | flag, curve=curve)
 
     def register_keys_p384(self, keys: Sequence[ECDSAPublicKey], device: int = -1) -> np.ndarray:
         """bh_keys384_register: build and keep the fixed-base tables of P-384 keys

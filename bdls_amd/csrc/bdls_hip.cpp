@@ -28,6 +28,7 @@
 
 #include "../../include/bdls_hip.h"
 #include "verify.h"
+#include "comb384.h"
 #include "keys384.h"
 #include "verify384.h"
 #include "pack.h"
@@ -58,6 +59,12 @@ hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg
 hipError_t launch_keys384_register(const KeyReg384& g, const uint8_t* pub, uint32_t n,
                                    uint8_t* status, uint32_t* fresh, uint32_t* bases,
                                    hipStream_t s);
+hipError_t launch_comb384_g(uint32_t* bases, uint32_t* side, uint32_t* gcomb, hipStream_t s);
+hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg384& g,
+                                 bool with_reg, const Comb384& cb, void* zero, size_t zero_bytes,
+                                 const Plan384& pl, const uint32_t* gtab, const uint32_t* gcomb,
+                                 uint32_t n, uint64_t* bitmap, uint8_t* reason, hipStream_t s,
+                                 hipStream_t aux, hipEvent_t fork, hipEvent_t join, hipEvent_t* ev);
 hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* gtab, uint32_t n,
                             uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev);
 size_t expand_temp_bytes(uint32_t m);
@@ -235,7 +242,10 @@ struct Dev {
   uint32_t* gtab384 = nullptr;  // fixed-base table of G
   DevBuf ws384;                 // Work384
   DevBuf in384, out384;         // bh_verify: one chunk's inputs / bitmap words + reasons
-  hipEvent_t ev384[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev384[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // BH_F_BATCH_KEYS (allocated at the device's first flagged P-384 pass, under mu)
+  uint32_t* gcomb384 = nullptr;  // comb of G
+  DevBuf comb384;                // Comb384: grouping tables and comb slots of one pass
   // bh_keys384_*: the P-384 key registry (allocated by reserve or the first register)
   DevBuf reg384_mem;
   bh::KeyReg384 reg384{};    // cap == 0: not allocated
@@ -545,6 +555,9 @@ void dev_free(Dev& d) {
     if (g) (void)hipFree(g);
   if (d.gtab384) (void)hipFree(d.gtab384);
   d.gtab384 = nullptr;
+  if (d.gcomb384) (void)hipFree(d.gcomb384);
+  d.gcomb384 = nullptr;
+  d.comb384.release();
   d.ws384.release();
   d.in384.release();
   d.out384.release();
@@ -1775,7 +1788,7 @@ constexpr uint32_t kWideHash = BH_F_HASH_SHA384 | BH_F_HASH_SHA512;
 // (nullptr: bh_verify and bh_verify_dev, which do).
 int check_flags(uint32_t flags, const char* fn = nullptr) {
   constexpr uint32_t known = BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_KEEP_KEYS |
-                             BH_F_HASH_SHA3_256 | BH_F_ANY_LANE | kWideHash;
+                             BH_F_HASH_SHA3_256 | BH_F_ANY_LANE | kWideHash | BH_F_BATCH_KEYS;
   if (flags & ~known) return fail(BH_E_INVALID, "unknown flag");
   if ((flags & BH_F_HASH_SHA256) && (flags & BH_F_HASH_SHA3_256))
     return fail(BH_E_INVALID, "BH_F_HASH_SHA256 and BH_F_HASH_SHA3_256 are exclusive");
@@ -1856,6 +1869,75 @@ int p384_setup(Dev& d, size_t m, bh::Work384* w, bh::Plan384* pl) {
   return BH_OK;
 }
 
+// Records of one key in a pass that earn the key a comb (BH_F_BATCH_KEYS):
+// BH_P384_COMB_MIN, parsed once, 2 .. 65535; default 4.
+uint32_t p384_comb_min() {
+  static const uint32_t v = [] {
+    const char* e = getenv("BH_P384_COMB_MIN");
+    const long x = e ? atol(e) : 0L;
+    return x > 0 ? (uint32_t)std::min(65535L, std::max(2L, x)) : bh::kComb384MinDefault;
+  }();
+  return v;
+}
+
+// Bytes of a flagged pass's grouping tables and comb slots for ns records.
+size_t comb384_hc(size_t ns) {
+  size_t hc = 128;
+  while (hc < 2 * ns) hc <<= 1;
+  return hc;
+}
+size_t comb384_cap(size_t ns) { return std::max<size_t>(1, ns / p384_comb_min()); }
+size_t comb384_bytes(size_t ns) {
+  return 256 + 3 * round256(4 * comb384_hc(ns)) + 2 * round256(4 * ns) +
+         round256(4 * comb384_cap(ns)) + round256(4 * comb384_cap(ns) * bh::kComb384BaseWords) +
+         2 * round256(4 * comb384_cap(ns) * bh::kComb384Words);
+}
+
+// The comb memory of a flagged P-384 pass of m records, and at the device's
+// first such pass the comb of G (caller holds d.mu, device set, p384_setup
+// done, nothing that uses the comb memory in flight if it has to grow).
+// *zero_bytes: the bytes from cb->ctr on that a pass clears.
+int p384_comb_setup(Dev& d, size_t m, bh::Comb384* cb, size_t* zero_bytes) {
+  const size_t ns = round64(m);
+  if (int rc = d.comb384.ensure(comb384_bytes(ns))) return rc;
+  const size_t hc = comb384_hc(ns), cap = comb384_cap(ns);
+  char* p = (char*)d.comb384.p;
+  auto take = [&](size_t bytes) {
+    char* q = p;
+    p += round256(bytes);
+    return q;
+  };
+  cb->hc = (uint32_t)hc;
+  cb->cap = (uint32_t)cap;
+  cb->min = p384_comb_min();
+  cb->ctr = (uint32_t*)take(8);
+  cb->rep = (uint32_t*)take(4 * hc);
+  cb->cnt = (uint32_t*)take(4 * hc);
+  *zero_bytes = (size_t)(p - (char*)d.comb384.p);
+  cb->gslot = (uint32_t*)take(4 * hc);
+  cb->bkt = (uint32_t*)take(4 * ns);
+  cb->list = (uint32_t*)take(4 * ns);
+  cb->slot_rep = (uint32_t*)take(4 * cap);
+  cb->bases = (uint32_t*)take(4 * cap * bh::kComb384BaseWords);
+  cb->side = (uint32_t*)take(4 * cap * bh::kComb384Words);
+  cb->tables = (uint32_t*)take(4 * cap * bh::kComb384Words);
+  if (!d.gcomb384) {
+    uint32_t* g = nullptr;
+    hipError_t e = hipMalloc(&g, bh::kComb384Words * 4);
+    if (e != hipSuccess) return fail(BH_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    // built by the code that builds a key's comb, with slot 0 as its scratch, on
+    // the device's own stream and waited for here, once
+    e = bh::launch_comb384_g(cb->bases, cb->side, g, d.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {
+      (void)hipFree(g);
+      return fail(BH_E_DEVICE, std::string("P-384 G comb: ") + hipGetErrorString(e));
+    }
+    d.gcomb384 = g;
+  }
+  return BH_OK;
+}
+
 // The P-384 passes of a device-resident batch on stream s, after every lane's
 // work (one workspace per device). Caller holds d.mu, device set, and counts
 // the batch for bh_device_stats (one per call of the C ABI). msg2_off /
@@ -1873,11 +1955,47 @@ int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bi
     if (int rc = sync_lanes(d)) return rc;
     if (ws384_bytes(round64(m)) > d.ws384.cap) HIPCHK(hipDeviceSynchronize());
     if (int rc = p384_setup(d, m, &w, &pl)) return rc;
+    bh::Comb384 cb{};
+    size_t cb_zero = 0;
+    if (flags & BH_F_BATCH_KEYS) {
+      if (comb384_bytes(round64(m)) > d.comb384.cap) HIPCHK(hipDeviceSynchronize());
+      if (int rc = p384_comb_setup(d, m, &cb, &cb_zero)) return rc;
+    }
     HIPCHK(wait_lanes(d, s));
     const bh::In384 in{b->pub + base * 96, b->sig,     b->sig_off + base, b->sig_len + base,
                        b->msg,             b->msg_off + base, b->msg_len + base,
                        flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256),
                        msg2_off ? msg2_off + base : nullptr, msg2_len ? msg2_len + base : nullptr};
+    if (flags & BH_F_BATCH_KEYS) {  // each chunk groups its records and plans three routes
+      bh::KeyReg384 reg = d.reg384;
+      if (!d.reg384_count) reg.cap = 0;  // nothing registered: no lookup, no registry route
+      HIPCHK(bh::launch_verify384_comb(in, w, reg, d.reg384_count != 0, cb, cb.ctr, cb_zero, pl,
+                                       d.gtab384, d.gcomb384, (uint32_t)m, bitmap + base / 64,
+                                       reason + base, s, d.aux, d.fork, d.join,
+                                       t ? d.ev384 : nullptr));
+      if (t) {
+        HIPCHK(hipEventSynchronize(d.ev384[6]));
+        // after the plan (ev384[3]) the ladder runs on s beside the comb build
+        // and, behind it (ev384[7]), the table routes on aux
+        float ms[6];
+        for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], d.ev384[k], d.ev384[k + 1]));
+        HIPCHK(hipEventElapsedTime(&ms[3], d.ev384[7], d.ev384[4]));
+        HIPCHK(hipEventElapsedTime(&ms[4], d.ev384[3], d.ev384[5]));
+        HIPCHK(hipEventElapsedTime(&ms[5], d.ev384[3], d.ev384[7]));
+        uint32_t cnt[2] = {0, 0}, ctr[2] = {0, 0};
+        HIPCHK(hipMemcpy(cnt, pl.cnt, 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ctr, cb.ctr, 8, hipMemcpyDeviceToHost));
+        t->prep_ms += ms[0];
+        t->inv_ms += ms[1];
+        t->plan_ms += ms[2];
+        t->keycomb_ms += ms[3];
+        t->build_ladder_ms += ms[4] + ms[5];
+        t->n_keycomb += cnt[0] + ctr[1];
+        t->n_ladder += (uint32_t)m - cnt[0] - ctr[1];
+        t->n_keytables += std::min(ctr[0], cb.cap);
+      }
+      continue;
+    }
     if (d.reg384_count) {  // keys registered: each chunk plans its own two routes
       HIPCHK(bh::launch_verify384_keys(in, w, d.reg384, pl, d.gtab384, (uint32_t)m,
                                        bitmap + base / 64, reason + base, s, d.aux, d.fork,
@@ -1931,7 +2049,8 @@ int run_dev_wide(Dev& d, int curve, const bh_batch* b, size_t n, uint32_t flags,
   if (t) *t = bh_timing{};
   const int ob = (flags & BH_F_HASH_SHA384) ? 48 : 64;
   const size_t kb = curve == BH_CURVE_P384 ? 96 : 64;
-  const uint32_t rest = flags & BH_F_NO_LOW_S;  // BH_F_KEEP_KEYS / BH_F_ANY_LANE: ignored
+  // BH_F_KEEP_KEYS / BH_F_ANY_LANE: ignored; BH_F_BATCH_KEYS: the P-384 pass's
+  const uint32_t rest = flags & (BH_F_NO_LOW_S | BH_F_BATCH_KEYS);
   // P-256: one digest pass ahead of the whole batch (run_dev splits by its own
   // bound): its pass builds key tables per pass, so passes of BH_P384_CHUNK
   // records would build the tables of the same keys again and again

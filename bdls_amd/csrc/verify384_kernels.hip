@@ -18,7 +18,16 @@
 //   k384_keys_insert  1 lane          the registry's one writer
 //   k384_keytab_bases 1 lane/key      the doubling chain, 96 window bases
 //   k384_keytab_rows  1 lane/window   15 affine entries, one inversion
-#include "keys384.h"
+//
+// A pass with BH_F_BATCH_KEYS (comb384.h) groups its records by key instead:
+//   k384_comb_group   1 lane/record   claim or find the key's bucket, count
+//   k384_comb_assign  1 lane/record   representatives: registry, comb slot or ladder
+//   k384_comb_plan    1 lane/record   the three index lists
+//   k384_comb_bases   1 lane/comb     the doubling chain, 6 bases
+//   k384_comb_rows    1 lane/comb     63 affine entries, one inversion
+//   k384_comb         1 lane/record   comb route: 64 doublings, u2 Q + u1 G folded
+//   k384_comb_g       1 lane          the comb of G, once per device
+#include "comb384.h"
 
 using namespace bh;
 
@@ -135,6 +144,106 @@ __global__ __launch_bounds__(64) void k384_keytab_rows(KeyReg384 g, const uint32
                        (size_t)win * kG384Ent * kG384Words);
 }
 
+// The claim of an empty bucket: the winner's value, ours or an earlier lane's.
+struct Cas384 {
+  __device__ uint32_t operator()(uint32_t* p, uint32_t v) const {
+    const uint32_t old = atomicCAS(p, 0u, v);
+    return old ? old : v;
+  }
+};
+
+__global__ __launch_bounds__(64) void k384_comb_group(In384 in, Work384 w, Comb384 cb, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t b = kNoSlot384;
+  if ((w.st[i] & 0x7fu) == R_OK) {
+    b = comb384_claim(in.pub, cb, i, Cas384{});
+    if (b != kNoSlot384) atomicAdd(&cb.cnt[b], 1u);
+  }
+  cb.bkt[i] = b;
+}
+
+__global__ __launch_bounds__(64) void k384_comb_assign(In384 in, KeyReg384 g, Comb384 cb, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t b = cb.bkt[i];
+  if (b == kNoSlot384 || cb.rep[b] != i + 1) return;
+  uint32_t r = comb384_group_route(in.pub, g, cb, i, b);
+  if (r == 0) {
+    r = atomicAdd(&cb.ctr[0], 1u);
+    if (r < cb.cap) cb.slot_rep[r] = i;
+    else r = kNoSlot384;  // (cap >= ns / min: not reached)
+  }
+  cb.gslot[b] = r;
+}
+
+__global__ __launch_bounds__(64) void k384_comb_plan(Comb384 cb, uint32_t n, Plan384 pl) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t slot = 0;
+  const int route = i < n ? comb384_record_route(cb, i, &slot) : -1;
+  // one route per wave downstream: each wave appends its records to the three lists
+  const uint64_t m0 = __ballot(route == 0), m1 = __ballot(route == 1), m2 = __ballot(route == 2);
+  uint32_t b0 = 0, b1 = 0, b2 = 0;
+  if (lane == 0) {
+    if (m0) b0 = atomicAdd(&pl.cnt[1], (uint32_t)__popcll(m0));
+    if (m1) b1 = atomicAdd(&cb.ctr[1], (uint32_t)__popcll(m1));
+    if (m2) b2 = atomicAdd(&pl.cnt[0], (uint32_t)__popcll(m2));
+  }
+  b0 = __shfl(b0, 0);
+  b1 = __shfl(b1, 0);
+  b2 = __shfl(b2, 0);
+  const uint64_t below = (1ull << lane) - 1;
+  if (route == 0) {
+    pl.lad_list[b0 + (uint32_t)__popcll(m0 & below)] = i;
+  } else if (route == 1) {
+    pl.slot[i] = slot;
+    cb.list[b1 + (uint32_t)__popcll(m1 & below)] = i;
+  } else if (route == 2) {
+    pl.slot[i] = slot;
+    pl.tab_list[b2 + (uint32_t)__popcll(m2 & below)] = i;
+  }
+}
+
+__global__ __launch_bounds__(64) void k384_comb_bases(Work384 w, Comb384 cb) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t ns = cb.ctr[0] < cb.cap ? cb.ctr[0] : cb.cap;
+  if (t >= ns) return;
+  const uint32_t i = cb.slot_rep[t];
+  uint32_t qx[14], qy[14];
+  ldw<14>(qx, w.qx, i, w.ns);
+  ldw<14>(qy, w.qy, i, w.ns);
+  comb384_bases(qx, qy, cb.bases + (size_t)t * kComb384BaseWords);
+}
+
+__global__ __launch_bounds__(64) void k384_comb_rows(Comb384 cb) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t ns = cb.ctr[0] < cb.cap ? cb.ctr[0] : cb.cap;
+  if (t >= ns) return;
+  comb384_rows(cb.bases + (size_t)t * kComb384BaseWords, cb.side + (size_t)t * kComb384Words,
+               cb.tables + (size_t)t * kComb384Words);
+}
+
+__global__ __launch_bounds__(64) void k384_comb(Work384 w, Comb384 cb, Plan384 pl,
+                                                const uint32_t* __restrict__ gcomb,
+                                                uint8_t* __restrict__ reason) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cb.ctr[1]) return;
+  const uint32_t i = cb.list[t];
+  const uint32_t* qtab = cb.tables + (size_t)pl.slot[i] * kComb384Words;
+  reason[i] = stage384_comb(w, qtab, gcomb, i) ? (uint8_t)R_OK : (uint8_t)R_MATH;
+}
+
+// bases: kComb384BaseWords, side: kComb384Words (scratch of the build), gcomb: the table
+__global__ __launch_bounds__(64) void k384_comb_g(uint32_t* bases, uint32_t* side, uint32_t* gcomb) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t gx[14], gy[14];
+  f384_const(gx, Cv_p384::gx_m);
+  f384_const(gy, Cv_p384::gy_m);
+  comb384_bases(gx, gy, bases);
+  comb384_rows(bases, side, gcomb);
+}
+
 __global__ __launch_bounds__(256) void k384_bitmap(const uint8_t* __restrict__ reason, uint32_t n,
                                                    uint64_t* __restrict__ bitmap) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -196,6 +305,59 @@ hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg
   if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
   if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
   hipLaunchKernelGGL(k384_keywin, grd, blk, 0, aux, w, g, pl, gtab, reason);
+  if (ev && (e = hipEventRecord(ev[4], aux)) != hipSuccess) return e;
+  if ((e = hipEventRecord(join, aux)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_ladder_list, grd, blk, 0, s, w, pl, gtab, reason);
+  if (ev && (e = hipEventRecord(ev[5], s)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
+  if (ev && (e = hipEventRecord(ev[6], s)) != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+// The comb of G into gcomb (kComb384Words), with a comb slot's bases and side as scratch.
+hipError_t launch_comb384_g(uint32_t* bases, uint32_t* side, uint32_t* gcomb, hipStream_t s) {
+  hipLaunchKernelGGL(k384_comb_g, dim3(1), dim3(64), 0, s, bases, side, gcomb);
+  return hipGetLastError();
+}
+
+// The pass with BH_F_BATCH_KEYS. zero / zero_bytes: cb's per-pass counters and
+// buckets (ctr, rep, cnt, contiguous), cleared here with pl.cnt. After the
+// inverse the records are grouped and routed; then, side by side, the ladder
+// list on s and on aux the comb build, the comb route and (with_reg: the
+// registry is not empty) the registry's table route. The list kernels are
+// launched for n lanes, the build kernels for cb.cap, and read their counts on
+// the device.
+// ev (optional): 8 events: prep, inverse, group + plan | end of the table
+// routes (on aux) | end of the ladder (on s) | end of the bitmap | ev[7]: end
+// of the comb build (on aux, before the table routes).
+hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg384& g,
+                                 bool with_reg, const Comb384& cb, void* zero, size_t zero_bytes,
+                                 const Plan384& pl, const uint32_t* gtab, const uint32_t* gcomb,
+                                 uint32_t n, uint64_t* bitmap, uint8_t* reason, hipStream_t s,
+                                 hipStream_t aux, hipEvent_t fork, hipEvent_t join, hipEvent_t* ev) {
+  if (n == 0) return hipSuccess;
+  hipError_t e;
+  const dim3 blk(64), grd((n + 63) / 64), grdk((cb.cap + 63) / 64);
+  if ((e = hipMemsetAsync(pl.cnt, 0, 8, s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(zero, 0, zero_bytes, s)) != hipSuccess) return e;
+  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_prep, grd, blk, 0, s, in, w, n);
+  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+  const uint32_t stride = (n + kInvChunk384 - 1) / kInvChunk384;
+  hipLaunchKernelGGL(k384_inv, dim3((stride + 63) / 64), blk, 0, s, w, stride, n);
+  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_comb_group, grd, blk, 0, s, in, w, cb, n);
+  hipLaunchKernelGGL(k384_comb_assign, grd, blk, 0, s, in, g, cb, n);
+  hipLaunchKernelGGL(k384_comb_plan, grd, blk, 0, s, cb, n, pl);
+  if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
+  if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_comb_bases, grdk, blk, 0, aux, w, cb);
+  hipLaunchKernelGGL(k384_comb_rows, grdk, blk, 0, aux, cb);
+  if (ev && (e = hipEventRecord(ev[7], aux)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_comb, grd, blk, 0, aux, w, cb, pl, gcomb, reason);
+  if (with_reg) hipLaunchKernelGGL(k384_keywin, grd, blk, 0, aux, w, g, pl, gtab, reason);
   if (ev && (e = hipEventRecord(ev[4], aux)) != hipSuccess) return e;
   if ((e = hipEventRecord(join, aux)) != hipSuccess) return e;
   hipLaunchKernelGGL(k384_ladder_list, grd, blk, 0, s, w, pl, gtab, reason);

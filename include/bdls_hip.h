@@ -96,6 +96,44 @@ extern "C" {
                                 resident P-256 batch in one pass). bh_timing.prep_ms includes
                                 the digest pass; bh_device_stats counts one batch per call.
                                 Every other entry point answers BH_E_INVALID for them. */
+#define BH_F_BATCH_KEYS 128u /* BH_CURVE_P384 passes: a key that at least 4 records of one pass
+                                (one chunk of BH_P384_CHUNK records) use, counting only the
+                                records that pass the checks before the curve arithmetic, gets
+                                a comb table for that pass -- 6 teeth x 64 bits, 63 affine
+                                entries, 7,056 bytes, built in library workspace and gone with
+                                the pass; nothing is registered or kept. Each record takes the
+                                first route that applies: its key is in the bh_keys384_*
+                                registry -> the registry's table route, as without the flag;
+                                its key has a comb -> the comb route (64 doublings with u1 G
+                                folded in from a comb of G, about 1,900 field products against
+                                the ladder's 5,600); otherwise the ladder, which also reports
+                                the reason of every record the checks rejected. Results never
+                                depend on the flag: bitmap and reasons are bit for bit those of
+                                the unflagged call, in bh_verify, bh_verify_dev and
+                                bh_verify_mixed's P-384 group, with every BH_F_HASH_* flag,
+                                two-span messages and BH_F_NO_LOW_S. Accepted by every entry
+                                point and ignored wherever the pass is not P-384 (a P-256 pass
+                                finds its repeated keys unasked). The comb of G, the grouping
+                                tables and the comb slots (one per 4 records of a chunk, about
+                                3.8 KB per record of the largest chunk) are allocated at a
+                                device's first flagged pass and freed by bh_shutdown; callers
+                                that never set the flag pay nothing.
+                                bh_timing of a flagged bh_verify_dev call, per chunk and
+                                summed: prep_ms and inv_ms as ever; plan_ms from the end of
+                                the inverse to the end of grouping and routing; then two
+                                streams run side by side from that point: the ladder route,
+                                and the comb build followed by the table routes (comb, then
+                                registry). build_ladder_ms = (routing end -> comb build end) +
+                                (routing end -> ladder end); keycomb_ms = comb build end ->
+                                end of both table routes; the two overlap in time, so they do
+                                not add up to the pass. n_keytables = combs built, n_keycomb =
+                                records on either table route, n_ladder = the rest.
+                                When to set it (65,536 resident records): 1.17 x
+                                at 16 and at 1,024 uses per key, 0.995 x on all-distinct keys,
+                                0.73 x at exactly 4 uses per key (the comb build, one lane per
+                                key, dominates there): set it for batches with a dozen or more
+                                records per key. BH_P384_COMB_MIN (2 .. 65535, read once) replaces the 4
+                                for experiments. */
 
 #define BH_CURVE_P256 0
 #define BH_CURVE_SECP256K1 1
@@ -108,7 +146,8 @@ extern "C" {
                            for P-256 (identity.Verify hashes with the MSP's family whatever the
                            key's curve, msp/identities.go:170-227); in digest mode any length
                            >= 1: the leftmost 48 bytes, a shorter digest whole, one reduction
-                           mod n. BH_F_KEEP_KEYS and BH_F_ANY_LANE are ignored. Every other
+                           mod n. BH_F_KEEP_KEYS and BH_F_ANY_LANE are ignored; BH_F_BATCH_KEYS
+                           gives keys repeated within a pass a comb for that pass. Every other
                            entry point answers BH_E_INVALID for this curve. */
 
 /* Bytes of one public key (X || Y) in bh_batch.pub for a curve: 64, 64, 96;
@@ -727,8 +766,8 @@ int bh_keys_count(int device, int curve, size_t *count);
  * (consensus.go:456-466, Config.Participants) for BDLS -- and results never
  * depend on it: same bitmap and reasons with or without, in bh_verify and
  * bh_verify_dev, with any BH_F_HASH_* flag. BH_F_KEEP_KEYS stays ignored for
- * P-384: tables are built by bh_keys384_register alone, never by a pass
- * (bh_timing.n_keytables stays 0; n_keycomb counts the records that took the
+ * P-384: kept tables are built by bh_keys384_register alone, never by a pass
+ * (without BH_F_BATCH_KEYS bh_timing.n_keytables stays 0; n_keycomb counts the records that took the
  * table route, plan_ms the lookup, keycomb_ms the table route, build_ladder_ms
  * the ladder; the two routes run side by side after the lookup, so these two
  * times overlap). bh_keys_* above keep refusing BH_CURVE_P384.
