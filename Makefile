@@ -12,7 +12,8 @@ HDRS := $(wildcard $(CSRC)/*.h) include/bdls_hip.h
 all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhostsim.so \
      tests/native/build/libhostsim384.so tests/native/build/libhostsim384k.so \
      tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so \
-     tests/native/build/libhostsimfused.so tests/native/build/libhostsim384c.so $(LIB)/csp_load
+     tests/native/build/libhostsimfused.so tests/native/build/libhostsim384c.so \
+     tests/native/build/libhostsimlltab.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -88,6 +89,19 @@ tests/native/build/libhostsim512.so: tests/native_sha512/hostsim_sha512.cpp $(HD
 tests/native/build/libhostsimfused.so: tests/native_fused/hostsim_fused.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
+
+# the per-batch comb table build (lltab_build) and j_dbl on their own
+tests/native/build/libhostsimlltab.so: tests/native_lltab/hostsim_lltab.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
+
+# stand-alone sanitizer run of lltab_build's scratch layout on the CPU
+# (tests/test_lltab_cpu.py builds and runs it)
+tests/native/build/lltab_selftest: tests/native_lltab/lltab_selftest.cpp \
+                                   tests/native_lltab/hostsim_lltab.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -o $@ $<
 
 # stand-alone sanitizer run of sha512.h on the CPU (tests/test_sha2wide_cpu.py builds and runs it)
 tests/native/build/sha512_selftest: tests/native_sha512/sha512_selftest.cpp $(HDRS)

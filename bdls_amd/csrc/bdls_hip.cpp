@@ -638,18 +638,20 @@ int env_route() {
 bh::LaunchOpts launch_opts(size_t m, uint32_t flags) {
   bh::LaunchOpts o;
   // records per inversion lane: ~2 waves per SIMD at 1M records (measured
-  // k_inv at 1M: 4 per lane 0.207 ms, 8 0.155, 16 0.159; 2 0.336). On the
-  // whole config-2 step, three alternating rounds on one box, 32 per lane was
-  // below 8 in every round by about 0.05 ms (5.346 / 5.308 / 5.287 against
-  // 5.417 / 5.354 / 5.338 ms), less than the 0.079 ms the default's own runs
-  // drifted over the call: the rule is kept and the question left open
-  // (DESIGN 4.11). BH_INV_CHUNK overrides for tuning
+  // k_inv at 1M: 4 per lane 0.207 ms, 8 0.155, 16 0.159; 2 0.336) below 2^20
+  // records. From 2^20 records on, 32 per lane: one safegcd inversion serves
+  // four times the records (k_inv: 89.8e6 -> 61.0e6 wave-instructions), and on the
+  // whole config-2 step, five alternating rounds in one call on one box, every
+  // 32 run lay below every 8 run (5.052 .. 5.075 against 5.086 .. 5.117 ms;
+  // profiles/ktab/chunk.json). BH_INV_CHUNK overrides for tuning
   static const long env_chunk = [] {
     const char* e = getenv("BH_INV_CHUNK");
     return e ? atol(e) : 0L;
   }();
   o.inv_chunk = env_chunk > 0 ? (uint32_t)std::min<long>(env_chunk, 64)
-                              : (uint32_t)std::max<size_t>(1, std::min<size_t>(16, m / 131072));
+                : m >= (size_t(1) << 20)
+                    ? 32u
+                    : (uint32_t)std::max<size_t>(1, std::min<size_t>(16, m / 131072));
   o.keep = (flags & BH_F_KEEP_KEYS) != 0;
   // kept tables pay off over later calls, so a second use in the batch is
   // enough; per-batch tables must pay off inside this batch

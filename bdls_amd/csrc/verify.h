@@ -1209,16 +1209,28 @@ BH_HD void q_keycomb(J30& A, bool& a_inf, const Work& w, uint32_t i, const uint3
 //   E[m] = H[m >> a] + L[m & (2^a - 1)],
 //   L[x] = sum_(i < a) (2 x_i - 1) B_i,
 //   H[y] = B_(t-1) + sum_(a <= i < t-1) (2 y_(i-a) - 1) B_i.
-// L and H (2^a + 2^(t-1-a) points) come from two Gray-code walks of mixed
-// additions of +-D_i (flipping digit i from -1 to +1 adds 2 B_i), made affine
-// with a second inversion; each entry is one affine addition H + L whose
-// denominators x_H - x_L are inverted together (a third inversion): 6 F_p ops
-// per entry instead of the full Gray walk over all entries (11 + 1) and its
-// backward affine pass (6), and no raw Jacobian entry written and read back.
+// The L points are closed under negation, L[~x & (2^a - 1)] = -L[x], so only
+// the half whose digit a - 1 is +1 is built,
+//   L'[x'] = B_(a-1) + sum_(i < a-1) (2 x'_i - 1) B_i = L[x' | 2^(a-1)],
+// and the entries come in SIGN PAIRS that share a denominator:
+//   E[(h << a) | 2^(a-1) | x']            = H[h] + L'[x'],
+//   E[(h << a) | (~x' & (2^(a-1) - 1))]   = H[h] - L'[x'].
+// L' and H (2^(a-1) + 2^(t-1-a) points, the same shape: a top point and a Gray
+// walk over the lower digits) come from two Gray-code walks of mixed additions
+// of +-D_i (flipping digit i from -1 to +1 adds 2 B_i), made affine with a
+// second inversion. Each of the 2^(t-2) pairs takes ONE denominator d = x_H -
+// x_L', inverted together (a third inversion: one prefix product and two
+// backward products per pair), and two affine additions
+//   lambda+- = (y_H -+ y_L') / d, x+- = lambda+-^2 - x_H - x_L',
+//   y+- = lambda+- (x_H - x+-) - y_H:
+// 4.5 F_p ops per entry instead of the full Gray walk over all entries (11 +
+// 1) and its backward affine pass (6), and no raw Jacobian entry written and
+// read back. At t = 7: 2,647 F_p ops per table (2,816 with all 2^a L points
+// and one denominator per entry).
 // No build step can degenerate: every scalar involved lies in (0, n / 2), the
 // walks' partial sums exceed every d_i they add with e + d < n, and H's scalar
-// (~2^(s (t-1))) never equals +-L's (< 2^(s a + 1)). The Horner additions keep
-// explicit degenerate handling (A = +-V_j only for crafted scalars), as a
+// (~2^(s (t-1))) never equals +-L''s (< 2^(s (a-1) + 1)). The Horner additions
+// keep explicit degenerate handling (A = +-V_j only for crafted scalars), as a
 // branch the lanes skip together.
 #ifndef BH_LL_T
 #define BH_LL_T 7  // teeth: 7 x 37 bits, 64 entries (signed)
@@ -1230,20 +1242,27 @@ constexpr uint32_t kLLAff = 20;                    // words per affine point
 // the build's split: L over the a low digits, H over the others + the top tooth
 constexpr int kLLA = (kLLTeeth - 1) / 2;
 constexpr uint32_t kLLNL = 1u << kLLA, kLLNH = 1u << (kLLTeeth - 1 - kLLA);
-constexpr uint32_t kLLWalk = kLLNL + kLLNH;         // L and H points (two walks)
+constexpr uint32_t kLLNLp = kLLNL / 2u;             // L' points: the L with digit a-1 = +1
+constexpr uint32_t kLLWalk = kLLNLp + kLLNH;        // L' and H points (two walks)
+constexpr uint32_t kLLPair = kLLEnt / 2u;           // sign pairs (H[h], L'[x']) of entries
 constexpr uint32_t kLLChain = 2u * (kLLTeeth - 1);  // Jacobian D_i / B_(i+1) of the chain
 // Table region (words): entries [0, kLLEnt) x kLLAff (all the comb reads), then
-// build scratch: affine B_0..B_(t-1), D_0..D_(t-2) (aux), affine L and H, raw
+// build scratch: affine B_0..B_(t-1), D_0..D_(t-2) (aux), affine L' and H, raw
 // Jacobian points (the chain's, then the walks'), running Z / denominator
-// products (12 words each).
+// products (12 words each: the chain's, the walks', then one per pair), kLLScr
+// words in all.
 constexpr uint32_t kLLAux = kLLEnt;
 constexpr uint32_t kLLLH = kLLAux + 2u * kLLTeeth - 1u;
 constexpr uint32_t kLLRaw = ((kLLLH + kLLWalk) * kLLAff + 3u) & ~3u;
 constexpr uint32_t kLLRawN = kLLChain > kLLWalk ? kLLChain : kLLWalk;
 constexpr uint32_t kLLPre = kLLRaw + 28u * kLLRawN;
+constexpr uint32_t kLLPreN = kLLRawN > kLLPair ? kLLRawN : kLLPair;
+constexpr uint32_t kLLScr = kLLPre + 12u * kLLPreN;
 static_assert(kLLTS >= 257 && kLLTS <= 288 && kLLSpace < 64 && kLLTeeth >= 3 &&
-                  kLLPre + 12u * kLLEnt <= kKTabWords && kLLChain <= kLLEnt &&
-                  kLLWalk <= kLLEnt,
+                  kLLScr <= kKTabWords && kLLChain <= kLLRawN && kLLWalk <= kLLRawN &&
+                  kLLChain <= kLLPreN && kLLWalk <= kLLPreN && kLLPair <= kLLPreN &&
+                  kLLNLp >= 1u && 2u * kLLNLp * kLLNH == kLLEnt && kLLRaw % 4u == 0u &&
+                  kLLPre % 4u == 0u,
               "comb table layout");
 
 BH_HD void llraw_store(uint32_t* tab, uint32_t b, const J30& P) { ktab_store(tab + kLLRaw, 0, b, P); }
@@ -1333,29 +1352,22 @@ BH_HD void ll_to_affine(uint32_t x[9], uint32_t y[9], const J30& E, const uint32
 // Walk position m (0..2^(t-1) - 1) -> entry gray(m); step m flips digit ctz(m).
 BH_HD uint32_t ll_gray(uint32_t m) { return m ^ (m >> 1); }
 
-// One Gray-code walk of the build (L or H): the 2^nd points
-//   P[g] = top + sum_(k < nd) (2 g_k - 1) B_(i0 + k)   (top = B_(t-1) for H, none for L),
+// One Gray-code walk of the build (L' or H): the 2^nd points
+//   P[g] = B_top + sum_(k < nd) (2 g_k - 1) B_(i0 + k)   (top = t-1 for H, a-1 for L'),
 // as raw Jacobian points at raw slots [r0, r0 + 2^nd) in walk order with the
 // running product z of their Z (the whole build's walks share one product
-// chain: pre slot r0 + m holds z after point m). Start: top - sum B_(i0 + k)
+// chain: pre slot r0 + m holds z after point m). Start: B_top - sum B_(i0 + k)
 // (mixed additions of -B, never degenerate); step m flips digit ctz(m) of
-// gray(m), adding +-D_(i0 + ctz(m)).
+// gray(m), adding +-D_(i0 + ctz(m)). nd = 0 (L' at t = 3, 4) is the one point B_top.
 template <class P>
-BH_HD void ll_walk(uint32_t* tab, uint32_t i0, int nd, bool top, uint32_t r0, uint32_t z[9],
+BH_HD void ll_walk(uint32_t* tab, uint32_t i0, int nd, uint32_t top, uint32_t r0, uint32_t z[9],
                    const uint32_t one[9]) {
   J30 A;
   bool same;
-  int k = nd - 1;
-  if (top) {
-    llaff_load(A.X, A.Y, tab, kLLAux + kLLTeeth - 1u);  // B_(t-1)
-  } else {  // -B_(i0 + nd - 1)
-    llaff_load(A.X, A.Y, tab, kLLAux + i0 + (uint32_t)k);
-    f_neg<P, 64>(A.Y, A.Y);
-    k--;
-  }
+  llaff_load(A.X, A.Y, tab, kLLAux + top);
   f_copy(A.Z, one);
 #pragma unroll 1
-  for (; k >= 0; k--) {
+  for (int k = nd - 1; k >= 0; k--) {
     uint32_t bx[9], by[9];
     llaff_load(bx, by, tab, kLLAux + i0 + (uint32_t)k);
     f_neg<P, 64>(by, by);
@@ -1443,55 +1455,62 @@ BH_HD void lltab_build(uint32_t* tab, const Work& w, uint32_t rec, uint32_t* scr
   ll_affine_back<P>(scr, kLLChain, inv, [](uint32_t c) {
     return (c & 1u) ? kLLAux + (c >> 1) + 1u : kLLAux + kLLTeeth + (c >> 1);
   });
-  // 2. L (digits 0 .. a-1) and H (digits a .. t-2 + the top tooth) by two
-  //    Gray walks into raw slots [0, NL) and [NL, NL + NH), one product chain,
-  //    made affine with one inversion into L / H slots (by Gray index).
-  ll_walk<P>(scr, 0u, kLLA, false, 0u, z, one);
-  ll_walk<P>(scr, (uint32_t)kLLA, kLLTeeth - 1 - kLLA, true, kLLNL, z, one);
+  // 2. L' (B_(a-1) + digits 0 .. a-2) and H (B_(t-1) + digits a .. t-2) by
+  //    two Gray walks into raw slots [0, NL') and [NL', NL' + NH), one product
+  //    chain, made affine with one inversion into L' / H slots (by Gray index).
+  ll_walk<P>(scr, 0u, kLLA - 1, (uint32_t)kLLA - 1u, 0u, z, one);
+  ll_walk<P>(scr, (uint32_t)kLLA, kLLTeeth - 1 - kLLA, (uint32_t)kLLTeeth - 1u, kLLNLp, z, one);
   f_inv_sg<P>(inv, z);
   ll_affine_back<P>(scr, kLLWalk, inv, [](uint32_t c) {
-    return kLLLH + (c < kLLNL ? ll_gray(c) : kLLNL + ll_gray(c - kLLNL));
+    return kLLLH + (c < kLLNLp ? ll_gray(c) : kLLNLp + ll_gray(c - kLLNLp));
   });
-  // 3. E[m] = H[m >> a] + L[m & (NL - 1)]: affine additions, the denominators
-  //    x_H - x_L inverted together. Forward: their running products (pre);
-  //    backward: lambda = (y_H - y_L) / (x_H - x_L), x = lambda^2 - x_H - x_L,
-  //    y = lambda (x_L - x) - y_L (beta 34 each: the comb's mixed additions
-  //    take beta <= 64).
+  // 3. The sign pairs p = h NL' + x': E[(h << a) | NL' | x'] = H[h] + L'[x']
+  //    and E[(h << a) | (~x' & (NL' - 1))] = H[h] - L'[x'], affine additions
+  //    on one denominator d = x_H - x_L'; the pairs' d inverted together.
+  //    Forward: their running products (pre); backward: lambda+- = (y_H -+
+  //    y_L') / d, x = lambda^2 - x_H - x_L', y = lambda (x_H - x) - y_H (beta
+  //    34 each: the comb's mixed additions take beta <= 64).
   uint32_t hx[9], hy[9], lx[9], ly[9], d[9];
 #pragma unroll 1
-  for (uint32_t m = 0; m < kLLEnt; m++) {
-    if ((m & (kLLNL - 1u)) == 0u) llaff_load(hx, hy, scr, kLLLH + kLLNL + (m >> kLLA));
-    llaff_load(lx, ly, scr, kLLLH + (m & (kLLNL - 1u)));
-    f_sub<P, 32>(d, hx, lx);                 // [b34], nonzero (H != +-L)
-    if (m == 0) f_copy(z, d);
+  for (uint32_t p = 0; p < kLLPair; p++) {
+    if ((p & (kLLNLp - 1u)) == 0u) llaff_load(hx, hy, scr, kLLLH + kLLNLp + p / kLLNLp);
+    llaff_load(lx, ly, scr, kLLLH + (p & (kLLNLp - 1u)));
+    f_sub<P, 32>(d, hx, lx);                 // [b34], nonzero (H != +-L')
+    if (p == 0) f_copy(z, d);
     else f_mul<P>(z, z, d);
-    if (m + 1u < kLLEnt) llpre_store(scr, m, z);
+    if (p + 1u < kLLPair) llpre_store(scr, p, z);
   }
   f_inv_sg<P>(inv, z);
 #pragma unroll 1
-  for (uint32_t m = kLLEnt; m-- > 0;) {
-    if (m == kLLEnt - 1u || (m & (kLLNL - 1u)) == kLLNL - 1u)
-      llaff_load(hx, hy, scr, kLLLH + kLLNL + (m >> kLLA));
-    llaff_load(lx, ly, scr, kLLLH + (m & (kLLNL - 1u)));
+  for (uint32_t p = kLLPair; p-- > 0;) {
+    const uint32_t h = p / kLLNLp, xl = p & (kLLNLp - 1u);
+    if (p == kLLPair - 1u || xl == kLLNLp - 1u) llaff_load(hx, hy, scr, kLLLH + kLLNLp + h);
+    llaff_load(lx, ly, scr, kLLLH + xl);
     f_sub<P, 32>(d, hx, lx);
-    uint32_t di[9], lam[9], t[9], x[9], y[9];
-    if (m > 0u) {
+    uint32_t di[9], sx[9];
+    if (p > 0u) {
       uint32_t pre[9];
-      llpre_load(pre, scr, m - 1u);
-      f_mul<P>(di, inv, pre);                // (x_H - x_L)^-1
+      llpre_load(pre, scr, p - 1u);
+      f_mul<P>(di, inv, pre);                // (x_H - x_L')^-1
       f_mul<P>(inv, inv, d);
     } else {
       f_copy(di, inv);
     }
-    f_sub<P, 32>(t, hy, ly);                 // [b34]
-    f_mul<P>(lam, t, di);                    // [b2]
-    f_sqr<P>(x, lam);                        // [b2]
-    f_add(t, hx, lx);                        // [b4]
-    f_sub<P, 32>(x, x, t);                   // [b34]
-    f_sub<P, 64>(t, lx, x);                  // [b66]
-    f_mul<P>(y, lam, t);                     // [b2]
-    f_sub<P, 32>(y, y, ly);                  // [b34]
-    llaff_store(tab, m, x, y);
+    f_add(sx, hx, lx);                       // [b4]
+#pragma unroll 1
+    for (int sg = 0; sg < 2; sg++) {         // sg 0: H + L', sg 1: H - L'
+      uint32_t lam[9], t[9], x[9], y[9];
+      if (sg == 0) f_sub<P, 32>(t, hy, ly);  // [b34]
+      else f_add(t, hy, ly);                 // [b4]
+      f_mul<P>(lam, t, di);                  // [b2]
+      f_sqr<P>(x, lam);                      // [b2]
+      f_sub<P, 32>(x, x, sx);                // [b34]
+      f_sub<P, 64>(t, hx, x);                // [b66]
+      f_mul<P>(y, lam, t);                   // [b2]
+      f_sub<P, 32>(y, y, hy);                // [b34]
+      const uint32_t lo = sg == 0 ? (kLLNLp | xl) : (~xl & (kLLNLp - 1u));
+      llaff_store(tab, (h << kLLA) | lo, x, y);
+    }
   }
 }
 
@@ -1505,7 +1524,7 @@ BH_HD void lltab_build(uint32_t* tab, const Work& w, uint32_t rec, uint32_t* scr
 // for the multi-lane kernels of small batches, which split the windows over
 // their lanes (a comb's doubling chain cannot be split): mixed additions, 11
 // F_p ops per window instead of 16. Per-batch tables keep one form each.
-constexpr uint32_t kRegWin = (kLLPre + 12u * kLLEnt + 3u) & ~3u;
+constexpr uint32_t kRegWin = (kLLScr + 3u) & ~3u;
 constexpr uint32_t kRegWinRaw = kRegWin + (uint32_t)kKWin * kKEnt * kLLAff;
 constexpr uint32_t kRegWinPre = kRegWinRaw + 28u * kKEnt;
 static_assert(kRegWinPre + 12u * kKEnt <= kKTabWords && kRegWin % 4 == 0, "registry slot layout");

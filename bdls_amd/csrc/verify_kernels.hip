@@ -700,7 +700,7 @@ __global__ __launch_bounds__(kRegWinBlock) void k_reg_win(Work w, Plan pl, KeyRe
   // the comb build's scratch at the slot's offsets (the entries' words unused):
   // LDS instead of the slot's global scratch, whose round trips (~1 us each on a
   // lone wave) made the build ~2.5x slower than its arithmetic
-  __shared__ __attribute__((aligned(16))) uint32_t s_comb[kLLPre + 12u * kLLEnt];
+  __shared__ __attribute__((aligned(16))) uint32_t s_comb[kLLScr];
   const uint32_t t = blockIdx.x;
   const uint32_t nt = min(pl.counters[2], pl.max_tables);
   if (t >= nt) return;  // the whole workgroup

@@ -108,7 +108,7 @@ __device__ uint32_t g_tab[kKTabWords];
 __device__ uint32_t g_q[2 * 9 * 64];
 template <bool LDS>
 __global__ void k_comb(uint64_t* out, uint32_t s, uint64_t* cyc) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_comb[kLLPre + 12u * kLLEnt];
+  __shared__ __attribute__((aligned(16))) uint32_t s_comb[kLLScr];
   Work w{};
   w.ns = 64;
   w.qx = g_q;
@@ -132,7 +132,7 @@ __global__ void k_comb(uint64_t* out, uint32_t s, uint64_t* cyc) {
 // lltab_build's first phase alone (the 222-doubling chain with its raw
 // stores and Z products), LDS scratch
 __global__ void k_comb_chain(uint64_t* out, uint32_t s, uint64_t* cyc) {
-  __shared__ __attribute__((aligned(16))) uint32_t scr[kLLPre + 12u * kLLEnt];
+  __shared__ __attribute__((aligned(16))) uint32_t scr[kLLScr];
   if (threadIdx.x != 0) return;
   J30 B;
   for (int k = 0; k < 9; k++) {
