@@ -13,7 +13,7 @@ all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhost
      tests/native/build/libhostsim384.so tests/native/build/libhostsim384k.so \
      tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so \
      tests/native/build/libhostsimfused.so tests/native/build/libhostsim384c.so \
-     tests/native/build/libhostsimlltab.so $(LIB)/csp_load
+     tests/native/build/libhostsimlltab.so tests/native/build/libhostsim384i.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -80,6 +80,21 @@ tests/native/build/libhostsim384c.so: tests/native_p384comb/hostsim384_comb.cpp 
                                       tests/native/hostsim384.cpp $(HDRS)
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
+
+# (hostsim384_idx.cpp includes hostsim384.cpp and adds the index-keyed passes' entries and the
+# packer at key width 96)
+tests/native/build/libhostsim384i.so: tests/native_p384idx/hostsim384_idx.cpp \
+                                      tests/native/hostsim384.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $< -lpthread
+
+# stand-alone sanitizer run of the index-keyed prep and grouping on the CPU
+# (tests/test_p384_batch_cpu.py builds and runs it)
+tests/native/build/idx384_selftest: tests/native_p384idx/hostsim384_idx.cpp \
+                                    tests/native/hostsim384.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -DIDX384_SELFTEST_MAIN -o $@ $< -lcrypto -lpthread
 
 tests/native/build/libhostsim512.so: tests/native_sha512/hostsim_sha512.cpp $(HDRS)
 	@mkdir -p tests/native/build

@@ -43,6 +43,8 @@ EXPORTS = (
     "bh_batch_verify_ptrs_submit", "bh_pack_stats", "bh_curve_key_bytes", "bh_verify_x509_ex",
     "bh_keys384_reserve", "bh_keys384_register", "bh_keys384_clear", "bh_keys384_count",
     "bh_verify_mixed",
+    "bh_verify384_compact", "bh_verify384_compact_submit", "bh_batch_verify384_ptrs",
+    "bh_batch_verify384_ptrs_submit",
 )
 KEY_FULL = 255  # bh_keys_register / bh_keys384_register status: registry full
 
@@ -213,6 +215,17 @@ def lib() -> ctypes.CDLL:
             L.bh_pack_stats.restype = i32
         except AttributeError:
             pass
+        # P-384 BatchVerify: the compact and the staged form, with job handles
+        L.bh_verify384_compact.argtypes = [ctypes.POINTER(BhCBatch), sz, u32, vp, vp]
+        L.bh_verify384_compact.restype = i32
+        L.bh_verify384_compact_submit.argtypes = [ctypes.POINTER(BhCBatch), sz, u32, vp, vp,
+                                                  ctypes.POINTER(vp)]
+        L.bh_verify384_compact_submit.restype = i32
+        L.bh_batch_verify384_ptrs.argtypes = [ctypes.POINTER(BhPBatch), sz, u32, vp, vp]
+        L.bh_batch_verify384_ptrs.restype = i32
+        L.bh_batch_verify384_ptrs_submit.argtypes = [ctypes.POINTER(BhPBatch), sz, u32, vp, vp,
+                                                     ctypes.POINTER(vp)]
+        L.bh_batch_verify384_ptrs_submit.restype = i32
         L.bh_host_alloc.argtypes = [sz, ctypes.POINTER(vp)]
         L.bh_host_alloc.restype = i32
         L.bh_host_free.argtypes = [vp]

@@ -175,6 +175,47 @@ def verify_packed(pub, sig, sig_off, sig_len, msg, msg_off, msg_len, flags: int 
     return valid, reason[:n]
 
 
+def verify_packed384(keys: Sequence[bytes], sigs: Sequence[bytes], msgs: Sequence[bytes],
+                     flags: int = 0, submit: bool = False):
+    """P-384 records as per-record buffers (96-byte keys X || Y, DER signatures,
+    messages or digests) through bh_batch_verify384_ptrs: the library
+    de-duplicates the keys by content, packs into its own page-locked staging and
+    deals the batch over every device. Returns (valid bool[n], reason u8[n]);
+    submit=True: a function that waits for the job (bh_verify_wait) and returns
+    them, so several batches can be in flight."""
+    _lib.ensure_init()
+    n = len(sigs)
+
+    def col(items):
+        bufs = [np.frombuffer(bytes(b) + b"\0", np.uint8) for b in items]
+        return bufs, np.array([a.ctypes.data for a in bufs] or [0], np.uint64)
+    kb, kp = col(keys)
+    sb, sp = col(sigs)
+    mb, mp = col(msgs)
+    sig_len = np.array([len(s) for s in sigs] or [0], np.uint32)
+    msg_len = np.array([len(m) for m in msgs] or [0], np.uint32)
+    bitmap = np.zeros((n + 7) // 8 or 1, dtype=np.uint8)
+    reason = np.zeros(n or 1, dtype=np.uint8)
+    b = _lib.BhPBatch(kp.ctypes.data, sp.ctypes.data, sig_len.ctypes.data, mp.ctypes.data,
+                      msg_len.ctypes.data)
+
+    def result():
+        return np.unpackbits(bitmap, bitorder="little")[:n].astype(bool), reason[:n]
+    if not submit:
+        _lib.check(_lib.lib().bh_batch_verify384_ptrs(ctypes.byref(b), n, flags,
+                                                      bitmap.ctypes.data, reason.ctypes.data))
+        return result()
+    job = ctypes.c_void_p()
+    _lib.check(_lib.lib().bh_batch_verify384_ptrs_submit(ctypes.byref(b), n, flags,
+                                                         bitmap.ctypes.data, reason.ctypes.data,
+                                                         ctypes.byref(job)))
+
+    def wait():   # (everything was copied when the submit call returned)
+        _lib.check(_lib.lib().bh_verify_wait(job))
+        return result()
+    return wait
+
+
 def verify_mixed(curve, pub, pub_off, sig, sig_off, sig_len, msg, msg_off, msg_len,
                  msg2_off=None, msg2_len=None, flags: int = 0):
     """Host-buffer batch of P-256 and P-384 records through bh_verify_mixed:
@@ -254,15 +295,20 @@ class HipCSP:
 
     # -- batch extensions
     def batch_verify(self, keys: Sequence[ECDSAPublicKey], signatures: Sequence[bytes],
-                     digests: Sequence[bytes]):
-        """Returns (valid bool[n], reason u8[n]); reason in ERROR_REASONS <=> Go error."""
+                     digests: Sequence[bytes], staged: bool = False):
+        """Returns (valid bool[n], reason u8[n]); reason in ERROR_REASONS <=> Go error.
+        staged=True (P-384 keys only): the batch goes as per-record buffers through
+        bh_batch_verify384_ptrs -- every device, keys imported once each."""
         curve = batch_curve(keys)
+        if staged and curve == _lib.BH_CURVE_P384:
+            return verify_packed384([k.raw() for k in keys], signatures, digests,
+                                    self._batch_flags(curve))
         return verify_packed(*pack_records(keys, signatures, digests),
                              flags=self._batch_flags(curve), curve=curve)
 
     def batch_identity_verify(self, keys: Sequence[ECDSAPublicKey], messages: Sequence[bytes],
                               signatures: Sequence[bytes], family: str = "SHA2",
-                              hash: str | None = None):
+                              hash: str | None = None, staged: bool = False):
         """msp/identities.go:170-199 for a whole batch with the MSP's hash family
         (SHA2 -> SHA-256, SHA3 -> SHA3-256) fused on device. hash ("SHA256",
         "SHA3_256", "SHA384", "SHA512") names the hash outright and overrides
@@ -271,6 +317,11 @@ class HipCSP:
         of the curve's pass."""
         flag = hash_flag(hash) if hash is not None else family_flag(family)
         curve = batch_curve(keys)
+        # staged (P-384 keys, a 256-bit hash): bh_batch_verify384_ptrs, as in batch_verify
+        if staged and curve == _lib.BH_CURVE_P384 and not flag & (
+                _lib.BH_F_HASH_SHA384 | _lib.BH_F_HASH_SHA512):
+            return verify_packed384([k.raw() for k in keys], signatures, messages,
+                                    self._batch_flags(curve) | flag)
         return verify_packed(*pack_records(keys, signatures, messages),
                              flags=self._batch_flags(curve) | flag, curve=curve)
 

@@ -59,6 +59,8 @@ hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg
 hipError_t launch_keys384_register(const KeyReg384& g, const uint8_t* pub, uint32_t n,
                                    uint8_t* status, uint32_t* fresh, uint32_t* bases,
                                    hipStream_t s);
+hipError_t launch_keys384_prep(const uint8_t* pub, const Keys384& kt, const KeyReg384& g,
+                               hipStream_t s);
 hipError_t launch_comb384_g(uint32_t* bases, uint32_t* side, uint32_t* gcomb, hipStream_t s);
 hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg384& g,
                                  bool with_reg, const Comb384& cb, void* zero, size_t zero_bytes,
@@ -216,6 +218,23 @@ struct Slot {
 // pass computes (3 slots left it idle ~0.3 ms per batch at config 2)
 constexpr int kSlots = 4;
 
+// One of a device's two P-384 pipeline slots (bh_verify384_compact,
+// bh_batch_verify384_ptrs): a whole shard at a time. Page-locked staging the
+// shard is packed into, its device copy with the shard's key workspace behind
+// it, the shard's bitmap words and reasons on the device and in page-locked
+// memory, and the events upload -> passes -> results. While the P-384 stream
+// runs one slot's chunks, the copy stream uploads the other slot's shard.
+struct Slot384 {
+  HostBuf hin;
+  DevBuf din;
+  DevBuf dout;
+  HostBuf hout{nullptr, 0, hipHostMallocPortable | hipHostMallocCoherent};
+  hipEvent_t uploaded = nullptr, done = nullptr;
+  bh_job* owner = nullptr;  // job whose results are in flight / sit in hout
+  size_t owner_part = 0;
+};
+constexpr int kSlots384 = 2;
+
 // The extra compute lanes of a device (round 3: one; round 4: up to
 // kMaxLanes - 1). Host-API batches rotate over lane 0 (Dev::stream / aux / ws)
 // and lanes 1.., each with its own workspace, so batch k+1's kernels run beside
@@ -251,6 +270,8 @@ struct Dev {
   bh::KeyReg384 reg384{};    // cap == 0: not allocated
   size_t reg384_count = 0;   // keys registered (the device's count, read back by register)
   DevBuf kb384;              // bh_keys384_register: keys, status, fresh slots, window bases
+  Slot384 s384[kSlots384];   // bh_verify384_compact / bh_batch_verify384_ptrs
+  uint32_t next_s384 = 0;
   // BH_F_HASH_SHA384 / BH_F_HASH_SHA512 (allocated at the device's first such call, under mu)
   DevBuf dig512;  // one chunk's digests, offsets and lengths: the curve pass's digest batch
   hipEvent_t ev512[2] = {nullptr, nullptr};
@@ -505,6 +526,11 @@ int dev_init(Dev& d, int id) {
                                                  (blocking_sync() ? hipEventBlockingSync : 0u)));
     HIPCHK(hipEventCreateWithFlags(&sl.keys_up, hipEventDisableTiming));
   }
+  for (Slot384& sl : d.s384) {
+    HIPCHK(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming |
+                                                 (blocking_sync() ? hipEventBlockingSync : 0u)));
+  }
   for (int c = 0; c < 2; c++) {
     HIPCHK(hipMalloc(&d.gtab[c], kGtabWords * 4));
     HIPCHK(bh::launch_gtab_build(c, d.gtab[c], d.stream));
@@ -566,6 +592,15 @@ void dev_free(Dev& d) {
   d.reg384_count = 0;
   g_reg384_gen.fetch_add(1, std::memory_order_relaxed);
   d.kb384.release();
+  for (Slot384& sl : d.s384) {
+    sl.hin.release();
+    sl.din.release();
+    sl.dout.release();
+    sl.hout.release();
+    if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
+    if (sl.done) (void)hipEventDestroy(sl.done);
+    sl.uploaded = sl.done = nullptr;
+  }
   d.dig512.release();
   for (auto& e : d.ev512) {
     if (e) (void)hipEventDestroy(e);
@@ -1175,6 +1210,7 @@ struct Part {
   size_t lo, m;
   bool done;
   bool small = false;  // latency path: reasons only (bitmap formed here)
+  bool p384 = false;   // slot indexes Dev::s384 (a P-384 shard), not Dev::slot
 };
 
 }  // namespace
@@ -1196,6 +1232,19 @@ int finish_part(bh_job* j, size_t k) {
   Part& p = j->parts[k];
   if (p.done) return BH_OK;
   Dev& d = *p.d;
+  if (p.p384) {
+    Slot384& s3 = d.s384[p.slot];
+    p.done = true;
+    s3.owner = nullptr;
+    HIPCHK(hipSetDevice(d.id));
+    hipError_t e3 = hipEventSynchronize(s3.done);
+    if (e3 != hipSuccess)
+      return fail(BH_E_DEVICE, std::string("pass failed: ") + hipGetErrorString(e3));
+    const uint64_t* w3 = (const uint64_t*)s3.hout.p;
+    bh::shard_bitmap_merge(j->bitmap, bh::Shard{p.lo, p.m}, w3);  // lo: a multiple of 64
+    std::memcpy(j->reason + p.lo, (const uint8_t*)(w3 + round64(p.m) / 64), p.m);
+    return BH_OK;
+  }
   Slot& sl = d.slot[p.slot];
   p.done = true;
   sl.owner = nullptr;
@@ -1634,7 +1683,8 @@ int wait_job(bh_job* j) {
     hipEvent_t ev = nullptr;
     {
       std::lock_guard<std::mutex> g(d.mu);
-      if (!j->parts[k].done) ev = d.slot[j->parts[k].slot].done;
+      const Part& pk = j->parts[k];
+      if (!pk.done) ev = pk.p384 ? d.s384[pk.slot].done : d.slot[pk.slot].done;
     }
     if (ev) {
       // no early return: every part is still collected (finish_part releases
@@ -1883,14 +1933,16 @@ uint32_t p384_comb_min() {
 }
 
 // Bytes of a flagged pass's grouping tables and comb slots for ns records.
-size_t comb384_hc(size_t ns) {
+// nk: the distinct keys of an index-keyed shard, whose buckets are the key
+// indices (0: the pass groups by fingerprint).
+size_t comb384_hc(size_t ns, size_t nk = 0) {
   size_t hc = 128;
-  while (hc < 2 * ns) hc <<= 1;
+  while (hc < 2 * ns || hc < nk) hc <<= 1;
   return hc;
 }
 size_t comb384_cap(size_t ns) { return std::max<size_t>(1, ns / p384_comb_min()); }
-size_t comb384_bytes(size_t ns) {
-  return 256 + 3 * round256(4 * comb384_hc(ns)) + 2 * round256(4 * ns) +
+size_t comb384_bytes(size_t ns, size_t nk = 0) {
+  return 256 + 3 * round256(4 * comb384_hc(ns, nk)) + 2 * round256(4 * ns) +
          round256(4 * comb384_cap(ns)) + round256(4 * comb384_cap(ns) * bh::kComb384BaseWords) +
          2 * round256(4 * comb384_cap(ns) * bh::kComb384Words);
 }
@@ -1899,10 +1951,10 @@ size_t comb384_bytes(size_t ns) {
 // first such pass the comb of G (caller holds d.mu, device set, p384_setup
 // done, nothing that uses the comb memory in flight if it has to grow).
 // *zero_bytes: the bytes from cb->ctr on that a pass clears.
-int p384_comb_setup(Dev& d, size_t m, bh::Comb384* cb, size_t* zero_bytes) {
+int p384_comb_setup(Dev& d, size_t m, bh::Comb384* cb, size_t* zero_bytes, size_t nk = 0) {
   const size_t ns = round64(m);
-  if (int rc = d.comb384.ensure(comb384_bytes(ns))) return rc;
-  const size_t hc = comb384_hc(ns), cap = comb384_cap(ns);
+  if (int rc = d.comb384.ensure(comb384_bytes(ns, nk))) return rc;
+  const size_t hc = comb384_hc(ns, nk), cap = comb384_cap(ns);
   char* p = (char*)d.comb384.p;
   auto take = [&](size_t bytes) {
     char* q = p;
@@ -2217,6 +2269,324 @@ int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, 
     for (size_t i = 0; i < (m + 7) / 8; i++)
       bitmap[base / 8 + i] = (uint8_t)(words[i / 8] >> (8 * (i % 8)));
   }
+  return BH_OK;
+}
+
+// ---- P-384 BatchVerify: compact keys, pipelined jobs, every device ---------------
+// bh_verify384_compact(_submit) and bh_batch_verify384_ptrs(_submit). A batch
+// is dealt over the devices in 64-aligned shards as submit_job deals them; a
+// shard is packed into one of its device's two Slot384s (page-locked), uploaded
+// on the copy stream, and run on the device's P-384 stream behind every lane's
+// work: the shard's distinct keys are imported once (k384_keys_prep), then its
+// chunks of BH_P384_CHUNK records pass one after the other over the device's
+// one Work384, writing into the shard's result buffer, which a last kernel
+// copies to page-locked memory ahead of the slot's done event. Nothing here
+// waits on the host unless a buffer has to grow or a slot still holds an
+// uncollected shard; the other slot's upload runs under this slot's passes.
+
+// Where a packed shard's arrays sit: in the slot's page-locked staging and, at
+// the same offsets, in its device copy; the key workspace follows on the device.
+struct Lay384 {
+  size_t m = 0, nk = 0;  // records; distinct keys (not indexed: one key per record)
+  bool indexed = false;
+  size_t sig_bytes = 0, msg_bytes = 0;
+  size_t o_keys = 0, o_idx = 0, o_soff = 0, o_moff = 0, o_slen = 0, o_mlen = 0, o_sig = 0,
+         o_msg = 0, total = 0;
+  size_t nks = 0, o_qx = 0, o_qy = 0, o_kst = 0, o_kslot = 0, dev_total = 0;  // device only
+};
+// nk_cap: keys the key region holds (the staged form reserves one per record
+// before it has de-duplicated them).
+Lay384 lay384(size_t m, size_t nk_cap, bool indexed, size_t sig_bytes, size_t msg_bytes) {
+  Lay384 L;
+  L.m = m;
+  L.nk = nk_cap;
+  L.indexed = indexed;
+  L.sig_bytes = sig_bytes;
+  L.msg_bytes = msg_bytes;
+  size_t p = 0;
+  auto take = [&](size_t bytes) {
+    const size_t q = p;
+    p += round256(bytes + 1);
+    return q;
+  };
+  L.o_keys = take(nk_cap * 96);
+  L.o_idx = take(m * 4);  // ... the small arrays: one upload, o_idx up to o_sig
+  L.o_soff = take(m * 8);
+  L.o_moff = take(m * 8);
+  L.o_slen = take(m * 4);
+  L.o_mlen = take(m * 4);
+  L.o_sig = take(sig_bytes + 8);
+  L.o_msg = take(msg_bytes + 8);
+  L.total = p;
+  L.nks = round64(std::max<size_t>(nk_cap, 1));
+  L.o_qx = take(56 * L.nks);
+  L.o_qy = take(56 * L.nks);
+  L.o_kst = take(L.nks);
+  L.o_kslot = take(4 * L.nks);
+  L.dev_total = p;
+  return L;
+}
+
+// Take the device's next P-384 slot, collecting the shard that still holds it
+// (caller holds d.mu).
+Slot384& take_slot384(Dev& d, int* k) {
+  *k = (int)(d.next_s384++ % kSlots384);
+  Slot384& sl = d.s384[*k];
+  if (sl.owner) {
+    bh_job* o = sl.owner;
+    int rc = finish_part(o, sl.owner_part);
+    if (rc && o->rc == BH_OK) {
+      o->rc = rc;
+      o->err = g_err;
+    }
+  }
+  return sl;
+}
+
+int ensure_slot384(Slot384& sl, const Lay384& L) {
+  int rc;
+  if ((rc = sl.hin.ensure(L.total + 256))) return rc;
+  if ((rc = sl.din.ensure(L.dev_total + 256))) return rc;
+  const size_t out_bytes = round64(L.m) / 8 + L.m + 1024;
+  if ((rc = sl.dout.ensure(out_bytes))) return rc;
+  return sl.hout.ensure(out_bytes);
+}
+
+// After a shard's upload is queued on the copy stream (sl.uploaded recorded):
+// the key import and the chunks' passes on the device's P-384 stream, the
+// results into the slot's page-locked buffer. Caller holds d.mu, device set.
+int launch_shard384(bh_job* j, Dev& d, int k, Slot384& sl, const Lay384& L, size_t lo,
+                    uint32_t flags) {
+  hipStream_t s = d.stream;
+  const size_t m = L.m;
+  char* dv = (char*)sl.din.p;
+  uint64_t* dbm = (uint64_t*)sl.dout.p;
+  uint8_t* drs = (uint8_t*)(dbm + round64(m) / 64);
+  HIPCHK(hipStreamWaitEvent(s, sl.uploaded, 0));
+  HIPCHK(wait_lanes(d, s));
+  bh::KeyReg384 reg = d.reg384;
+  if (!d.reg384_count) reg.cap = 0;  // nothing registered: no lookup, no registry route
+  bh::Keys384 kt{};
+  if (L.indexed) {  // once per shard: every chunk reads the key workspace
+    kt.nk = (uint32_t)L.nk;
+    kt.nks = (uint32_t)L.nks;
+    kt.qx = (uint32_t*)(dv + L.o_qx);
+    kt.qy = (uint32_t*)(dv + L.o_qy);
+    kt.st = (uint8_t*)(dv + L.o_kst);
+    kt.slot = (uint32_t*)(dv + L.o_kslot);
+    HIPCHK(bh::launch_keys384_prep((const uint8_t*)(dv + L.o_keys), kt, reg, s));
+  }
+  const size_t chunk = p384_chunk();
+  for (size_t base = 0; base < m; base += chunk) {
+    const size_t mc = std::min(chunk, m - base);
+    bh::Work384 w;
+    bh::Plan384 pl;
+    // the one workspace of the device: it grows only with nothing in flight
+    if (ws384_bytes(round64(mc)) > d.ws384.cap) HIPCHK(hipDeviceSynchronize());
+    if (int rc = p384_setup(d, mc, &w, &pl)) return rc;
+    bh::Comb384 cb{};
+    size_t cb_zero = 0;
+    if (flags & BH_F_BATCH_KEYS) {
+      const size_t nk = L.indexed ? L.nk : 0;
+      if (comb384_bytes(round64(mc), nk) > d.comb384.cap) HIPCHK(hipDeviceSynchronize());
+      if (int rc = p384_comb_setup(d, mc, &cb, &cb_zero, nk)) return rc;
+    }
+    bh::In384 in{(const uint8_t*)(dv + L.o_keys) + (L.indexed ? 0 : base * 96),
+                 (const uint8_t*)(dv + L.o_sig),
+                 (const uint64_t*)(dv + L.o_soff) + base,
+                 (const uint32_t*)(dv + L.o_slen) + base,
+                 (const uint8_t*)(dv + L.o_msg),
+                 (const uint64_t*)(dv + L.o_moff) + base,
+                 (const uint32_t*)(dv + L.o_mlen) + base,
+                 flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256)};
+    if (L.indexed) {
+      in.key_idx = (const uint32_t*)(dv + L.o_idx) + base;
+      in.kt = kt;
+    }
+    if (flags & BH_F_BATCH_KEYS) {
+      HIPCHK(bh::launch_verify384_comb(in, w, reg, d.reg384_count != 0, cb, cb.ctr, cb_zero, pl,
+                                       d.gtab384, d.gcomb384, (uint32_t)mc, dbm + base / 64,
+                                       drs + base, s, d.aux, d.fork, d.join, nullptr));
+    } else if (d.reg384_count) {
+      HIPCHK(bh::launch_verify384_keys(in, w, d.reg384, pl, d.gtab384, (uint32_t)mc,
+                                       dbm + base / 64, drs + base, s, d.aux, d.fork, d.join,
+                                       nullptr));
+    } else {
+      HIPCHK(bh::launch_verify384(in, w, d.gtab384, (uint32_t)mc, dbm + base / 64, drs + base, s,
+                                  nullptr));
+    }
+  }
+  // a kernel, not a D2H copy, for launch_part's reason: the copy engine's next
+  // command is the other slot's upload
+  HIPCHK(bh::launch_result_out(dbm, sl.hout.p, round64(m) / 8 + m, s));
+  HIPCHK(hipEventRecord(sl.done, s));
+  HIPCHK(hipEventRecord(d.done, s));
+  d.done_recorded = true;
+  sl.owner = j;
+  sl.owner_part = j->parts.size();
+  Part part{&d, k, lo, m, false};
+  part.p384 = true;
+  j->parts.push_back(part);
+  return BH_OK;
+}
+
+// Shard [lo, lo + m) of a compact batch with 96-byte keys: only the keys its
+// records use, indices rebased (remap: nkeys entries of UINT32_MAX, left so).
+// s0 / m0: the shard's first signature / message byte; *sb / *mb: its bytes.
+int enqueue384_compact(bh_job* j, Dev& d, const bh_cbatch& c, size_t lo, size_t m, uint64_t s0,
+                       uint64_t m0, uint32_t flags, std::vector<uint32_t>& remap, uint64_t* sb,
+                       uint64_t* mb) {
+  HIPCHK(hipSetDevice(d.id));
+  int k;
+  Slot384& sl = take_slot384(d, &k);
+  uint64_t sbytes = 0, mbytes = 0;
+  for (size_t i = lo; i < lo + m; i++) {
+    sbytes += c.sig_len[i];
+    mbytes += c.msg_len ? c.msg_len[i] : c.msg_stride;
+  }
+  *sb = sbytes;
+  *mb = mbytes;
+  std::vector<uint32_t> used, lidx;  // the shard's keys in first-use order; rebased indices
+  if (c.key_idx) {
+    lidx.resize(m);
+    for (size_t i = 0; i < m; i++) {
+      const uint32_t g = c.key_idx[lo + i];
+      if (remap[g] == UINT32_MAX) {
+        remap[g] = (uint32_t)used.size();
+        used.push_back(g);
+      }
+      lidx[i] = remap[g];
+    }
+    for (uint32_t g : used) remap[g] = UINT32_MAX;
+  }
+  const Lay384 L = lay384(m, c.key_idx ? used.size() : m, c.key_idx != nullptr, sbytes, mbytes);
+  if (int rc = ensure_slot384(sl, L)) return rc;
+  char* h = (char*)sl.hin.p;
+  if (c.key_idx) {
+    for (size_t t = 0; t < used.size(); t++)
+      std::memcpy(h + L.o_keys + t * 96, c.keys + (size_t)used[t] * 96, 96);
+    std::memcpy(h + L.o_idx, lidx.data(), m * 4);
+  } else {
+    std::memcpy(h + L.o_keys, c.keys + lo * 96, m * 96);
+  }
+  uint64_t* soff = (uint64_t*)(h + L.o_soff);
+  uint64_t* moff = (uint64_t*)(h + L.o_moff);
+  uint32_t* slen = (uint32_t*)(h + L.o_slen);
+  uint32_t* mlen = (uint32_t*)(h + L.o_mlen);
+  uint64_t sp = 0, mp = 0;
+  for (size_t i = 0; i < m; i++) {
+    soff[i] = sp;
+    moff[i] = mp;
+    sp += slen[i] = c.sig_len[lo + i];
+    mp += mlen[i] = c.msg_len ? c.msg_len[lo + i] : c.msg_stride;
+  }
+  if (sbytes) std::memcpy(h + L.o_sig, c.sig + s0, sbytes);
+  if (mbytes) std::memcpy(h + L.o_msg, c.msg + m0, mbytes);
+  HIPCHK(hipMemcpyAsync(sl.din.p, h, L.total, hipMemcpyHostToDevice, d.copy));
+  HIPCHK(hipEventRecord(sl.uploaded, d.copy));
+  return launch_shard384(j, d, k, sl, L, lo, flags);
+}
+
+const uint8_t kZeroKey384[96] = {0};
+struct SrcPtrs384 {  // SrcPtrs with 96-byte keys
+  const bh_pbatch* b;
+  const uint8_t* key(size_t i) const { return b->pub[i] ? b->pub[i] : kZeroKey384; }
+  const uint8_t* sig(size_t i) const { return b->sig[i]; }
+  uint32_t sig_len(size_t i) const { return b->sig[i] ? b->sig_len[i] : 0u; }
+  const uint8_t* msg(size_t i) const { return b->msg[i]; }
+  uint32_t msg_len(size_t i) const { return b->msg[i] ? b->msg_len[i] : 0u; }
+};
+
+// the 96-byte packer (its own worker pool, made at the first staged P-384 batch)
+std::mutex g_pack384_mu;
+bh::pack::PackerT<96>& packer384() {
+  static auto* p = new bh::pack::PackerT<96>(bh::pack::default_threads());
+  return *p;
+}
+
+// Shard [lo, lo + m) of the caller's per-record buffers, packed by pack.h into
+// the slot's page-locked staging: keys de-duplicated by content, the bytes'
+// chunks uploaded as each completes, then the keys, indices, offsets and
+// lengths. Everything is copied when this returns. Caller holds d.mu.
+int enqueue384_staged(bh_job* j, Dev& d, const SrcPtrs384& src, size_t lo, size_t m,
+                      uint32_t flags) {
+  HIPCHK(hipSetDevice(d.id));
+  int k;
+  Slot384& sl = take_slot384(d, &k);
+  std::lock_guard<std::mutex> pg(g_pack384_mu);
+  bh::pack::PackerT<96>& P = packer384();
+  bh::pack::Result r;
+  P.plan(src, lo, m, &r, 1);  // always de-duplicated: the pass is index-keyed
+  Lay384 L = lay384(m, m, true, r.sig_bytes, r.msg_bytes);
+  if (int rc = ensure_slot384(sl, L)) return rc;
+  char* h = (char*)sl.hin.p;
+  char* dv = (char*)sl.din.p;
+  bh::pack::Out out{(uint8_t*)(h + L.o_keys), (uint32_t*)(h + L.o_idx), (uint32_t*)(h + L.o_slen),
+                    (uint32_t*)(h + L.o_mlen)};
+  uint64_t* soff = (uint64_t*)(h + L.o_soff);
+  uint64_t* moff = (uint64_t*)(h + L.o_moff);
+  uint64_t sp = 0, mp = 0;
+  for (size_t i = 0; i < m; i++) {  // the packer writes the bytes in record order
+    soff[i] = sp;
+    moff[i] = mp;
+    sp += src.sig_len(lo + i);
+    mp += src.msg_len(lo + i);
+  }
+  hipError_t ce = hipSuccess;
+  auto h2d = [&](size_t off, size_t bytes) {
+    if (ce == hipSuccess && bytes)
+      ce = hipMemcpyAsync(dv + off, h + off, bytes, hipMemcpyHostToDevice, d.copy);
+  };
+  P.fill(src, out, (uint8_t*)(h + L.o_sig), (uint8_t*)(h + L.o_msg), &r, [&](int c) {
+    h2d(L.o_sig + r.sig_chunk[c], r.sig_chunk[c + 1] - r.sig_chunk[c]);
+    h2d(L.o_msg + r.msg_chunk[c], r.msg_chunk[c + 1] - r.msg_chunk[c]);
+  });
+  L.nk = r.nkeys;  // <= m; ids the claim blocks left unused are zero keys no record names
+  h2d(L.o_keys, L.nk * 96);
+  h2d(L.o_idx, L.o_sig - L.o_idx);
+  HIPCHK(ce);
+  HIPCHK(hipEventRecord(sl.uploaded, d.copy));
+  return launch_shard384(j, d, k, sl, L, lo, flags);
+}
+
+// The shards of a P-384 batch over all initialised devices, BH_HOST_SHARDS per
+// device, dealt as submit_job deals them; enq(j, d, lo, len) under d.mu. One
+// batch for bh_device_stats, however many shards and chunks.
+template <class Enq>
+int submit384(size_t n, uint8_t* bitmap, uint8_t* reason, bh_job** out, Enq enq) {
+  *out = nullptr;
+  std::vector<Dev*> devs = all_devs();
+  if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
+  bh_job* j = new bh_job();
+  j->bitmap = bitmap;
+  j->reason = reason;
+  j->n = n;
+  if (n) {
+    std::memset(bitmap, 0, (n + 7) / 8);
+    g_dev_batches.fetch_add(1, std::memory_order_relaxed);
+    g_dev_records.fetch_add(n, std::memory_order_relaxed);
+  }
+  static const size_t per = [] {  // read once, like BH_P384_CHUNK
+    const char* e = getenv("BH_HOST_SHARDS");
+    return e ? (size_t)std::max(1, std::min(atoi(e), 8)) : size_t(1);
+  }();
+  const size_t nd = bh::shard_devices(n, devs.size() * per);
+  for (size_t k = 0; k < nd; k++) {
+    const bh::Shard sh = bh::shard_of(n, nd, k);
+    if (!sh.len) break;
+    Dev& d = *devs[k % devs.size()];
+    int rc;
+    {
+      std::lock_guard<std::mutex> g(d.mu);
+      rc = enq(j, d, sh.lo, sh.len);
+    }
+    if (rc) {
+      const std::string err = g_err;
+      (void)wait_job(j);  // drain what was enqueued
+      return fail(rc, err);
+    }
+  }
+  *out = j;
   return BH_OK;
 }
 
@@ -2911,6 +3281,70 @@ int bh_batch_verify_ptrs(int curve, const bh_pbatch* b, size_t n, uint32_t flags
                          uint8_t* bitmap, uint8_t* reason) {
   bh_job* j = nullptr;
   if (int rc = bh_batch_verify_ptrs_submit(curve, b, n, flags, bitmap, reason, &j)) return rc;
+  return wait_job(j);
+}
+
+// ---- P-384 BatchVerify (submit384) ----
+// Everything but the device: flags, size, required fields, key indices and
+// the byte buffers the lengths call for.
+static int check_compact384(const bh_cbatch* b, size_t n, uint32_t flags, const uint8_t* bitmap,
+                            const uint8_t* reason, const char* fn) {
+  if (int rc = check_flags(flags, fn)) return rc;
+  if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
+  if (int rc = check_compact(b, n, bitmap, reason)) return rc;
+  if (!n) return BH_OK;
+  bool sig = false, msg = b->msg_len ? false : b->msg_stride != 0;
+  for (size_t i = 0; i < n && !(sig && msg); i++) {
+    sig |= b->sig_len[i] != 0;
+    if (b->msg_len) msg |= b->msg_len[i] != 0;
+  }
+  if ((sig && !b->sig) || (msg && !b->msg)) return fail(BH_E_INVALID, "null pointer in batch");
+  return BH_OK;
+}
+
+int bh_verify384_compact_submit(const bh_cbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+                                uint8_t* reason, bh_job** job) {
+  if (!job) return fail(BH_E_INVALID, "null job");
+  *job = nullptr;
+  if (int rc = check_compact384(b, n, flags, bitmap, reason, "bh_verify384_compact")) return rc;
+  std::vector<uint32_t> remap;
+  if (n && b->key_idx && !all_devs().empty()) remap.assign(b->nkeys, UINT32_MAX);
+  uint64_t s0 = 0, m0 = 0;  // the shards come in order: running byte offsets
+  return submit384(n, bitmap, reason, job, [&](bh_job* j, Dev& d, size_t lo, size_t len) {
+    uint64_t sb = 0, mb = 0;
+    const int rc = enqueue384_compact(j, d, *b, lo, len, s0, m0, flags, remap, &sb, &mb);
+    s0 += sb;
+    m0 += mb;
+    return rc;
+  });
+}
+
+int bh_verify384_compact(const bh_cbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+                         uint8_t* reason) {
+  bh_job* j = nullptr;
+  if (int rc = bh_verify384_compact_submit(b, n, flags, bitmap, reason, &j)) return rc;
+  return wait_job(j);
+}
+
+int bh_batch_verify384_ptrs_submit(const bh_pbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+                                   uint8_t* reason, bh_job** job) {
+  if (!job) return fail(BH_E_INVALID, "null job");
+  *job = nullptr;
+  if (!b || (n && (!b->pub || !b->sig || !b->sig_len || !b->msg || !b->msg_len || !bitmap ||
+                   !reason)))
+    return fail(BH_E_INVALID, "null pointer in batch");
+  if (int rc = check_flags(flags, "bh_batch_verify384_ptrs")) return rc;
+  if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
+  const SrcPtrs384 src{b};
+  return submit384(n, bitmap, reason, job, [&](bh_job* j, Dev& d, size_t lo, size_t len) {
+    return enqueue384_staged(j, d, src, lo, len, flags);
+  });
+}
+
+int bh_batch_verify384_ptrs(const bh_pbatch* b, size_t n, uint32_t flags, uint8_t* bitmap,
+                            uint8_t* reason) {
+  bh_job* j = nullptr;
+  if (int rc = bh_batch_verify384_ptrs_submit(b, n, flags, bitmap, reason, &j)) return rc;
   return wait_job(j);
 }
 

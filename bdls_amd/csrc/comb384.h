@@ -14,6 +14,9 @@
 //               probing, every hit confirmed on all 24 key words. A bucket holds
 //               the index + 1 of the record that claimed it (the group's
 //               representative) and the group's count.
+//               An index-keyed pass (In384::key_idx) skips all of this: its
+//               buckets are the key indices, one atomic addition per record
+//               (comb384_index_route below).
 //   routing     per group, by its representative: registered keys to the
 //               registry's route, groups of >= min records to a comb slot, the
 //               rest (and every record prep rejected) to the ladder.
@@ -55,9 +58,9 @@ struct Comb384 {
   uint32_t* tables;    // [cap][kComb384Words]
 };
 
-BH_HD bool comb384_same_key(const uint8_t* pub, uint32_t rec, const uint32_t k[24]) {
+BH_HD bool comb384_same_key(const In384& in, uint32_t rec, const uint32_t k[24]) {
   uint32_t q[24];
-  key384_words(pub + (size_t)rec * 96, q);
+  key384_words(in384_key(in, rec), q);
   uint32_t d = 0;
 #pragma unroll
   for (int j = 0; j < 24; j++) d |= q[j] ^ k[j];
@@ -69,14 +72,14 @@ BH_HD bool comb384_same_key(const uint8_t* pub, uint32_t rec, const uint32_t k[2
 // claim). kNoSlot384 only if every bucket is taken by another key, which
 // hc >= 2 ns rules out. The caller counts the record into cnt[bucket].
 template <class Cas>
-BH_HD uint32_t comb384_claim(const uint8_t* pub, const Comb384& cb, uint32_t i, Cas cas) {
+BH_HD uint32_t comb384_claim(const In384& in, const Comb384& cb, uint32_t i, Cas cas) {
   uint32_t k[24];
-  key384_words(pub + (size_t)i * 96, k);
+  key384_words(in384_key(in, i), k);
   uint32_t b = key384_hash(k) & (cb.hc - 1);
   for (uint32_t probes = 0; probes < cb.hc; probes++, b = (b + 1) & (cb.hc - 1)) {
     uint32_t v = cb.rep[b];
     if (v == 0) v = cas(&cb.rep[b], i + 1);
-    if (v == i + 1 || comb384_same_key(pub, v - 1, k)) return b;
+    if (v == i + 1 || comb384_same_key(in, v - 1, k)) return b;
   }
   return kNoSlot384;
 }
@@ -84,15 +87,40 @@ BH_HD uint32_t comb384_claim(const uint8_t* pub, const Comb384& cb, uint32_t i, 
 // What the group of bucket b gets, asked by its representative i once every
 // record is counted: its registry slot | kComb384Reg, kNoSlot384 (ladder), or 0
 // for "a comb slot", which the caller hands out.
-BH_HD uint32_t comb384_group_route(const uint8_t* pub, const KeyReg384& g, const Comb384& cb,
+BH_HD uint32_t comb384_group_route(const In384& in, const KeyReg384& g, const Comb384& cb,
                                    uint32_t i, uint32_t b) {
   if (g.cap) {
     uint32_t k[24];
-    key384_words(pub + (size_t)i * 96, k);
+    key384_words(in384_key(in, i), k);
     const uint32_t s = keys384_find(g, k);
     if (s != kNoSlot384) return s | kComb384Reg;
   }
   return cb.cnt[b] >= cb.min ? 0u : kNoSlot384;
+}
+
+// The expanded layout by its key bytes alone (key i at pub + 96 i).
+template <class Cas>
+BH_HD uint32_t comb384_claim(const uint8_t* pub, const Comb384& cb, uint32_t i, Cas cas) {
+  return comb384_claim(In384{pub}, cb, i, cas);
+}
+BH_HD uint32_t comb384_group_route(const uint8_t* pub, const KeyReg384& g, const Comb384& cb,
+                                   uint32_t i, uint32_t b) {
+  return comb384_group_route(In384{pub}, g, cb, i, b);
+}
+
+// Index-keyed passes (In384::key_idx) group by key index instead: bucket j is
+// key j (hc >= kt.nk), a record that prep admitted adds one to cnt[key_idx[i]]
+// (the caller's atomic addition) and has bkt[i] = key_idx[i]; no fingerprint,
+// no claim, no representative. Two indices whose 96 bytes are equal are two
+// groups. What key j's group gets, asked once per key when every record is
+// counted: as comb384_group_route, the registry slot being the one
+// keys384_prep found. A comb slot's slot_rep is then the key index, and its
+// bases come from the key workspace.
+BH_HD uint32_t comb384_index_route(const Keys384& kt, const Comb384& cb, uint32_t j) {
+  if (cb.cnt[j] == 0) return kNoSlot384;  // (no record reads it)
+  const uint32_t s = kt.slot[j];
+  if (s != kNoSlot384) return s | kComb384Reg;
+  return cb.cnt[j] >= cb.min ? 0u : kNoSlot384;
 }
 
 // Record i's route from its group's: 0 ladder, 1 comb, 2 registry; *slot is the

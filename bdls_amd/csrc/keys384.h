@@ -195,9 +195,30 @@ BH_HD void keytab384_window(const uint32_t* base, uint32_t* rows) {
 // stays on the ladder route, which reports its reason.
 BH_HD uint32_t stage384_plan(const In384& in, const Work384& w, const KeyReg384& g, uint32_t i) {
   if ((w.st[i] & 0x7fu) != R_OK) return kNoSlot384;
+  if (in.key_idx) return in.kt.slot[in.key_idx[i]];  // looked up once per key (keys384_prep)
   uint32_t k[24];
-  key384_words(in.pub + (size_t)i * 96, k);
+  key384_words(in384_key(in, i), k);
   return keys384_find(g, k);
+}
+
+// Key j of an index-keyed shard, once for all its records and chunks:
+// key_import384's verdict and coordinates into the key workspace, and the
+// key's slot in the registry (g.cap == 0: no registry, no lookup).
+BH_HD void keys384_prep(const uint8_t* pub, const Keys384& kt, const KeyReg384& g, uint32_t j) {
+  uint32_t qx[14], qy[14];
+  const bool ok = key_import384(pub + (size_t)j * 96, qx, qy);
+  uint32_t slot = kNoSlot384;
+  if (ok) {
+    stw<14>(kt.qx, j, kt.nks, qx);
+    stw<14>(kt.qy, j, kt.nks, qy);
+    if (g.cap) {
+      uint32_t k[24];
+      key384_words(pub + (size_t)j * 96, k);
+      slot = keys384_find(g, k);
+    }
+  }
+  kt.st[j] = ok ? (uint8_t)R_OK : (uint8_t)R_BAD_KEY;
+  kt.slot[j] = slot;
 }
 
 // Record i on the table route: true iff x(u1 G + u2 Q) mod n == r. qtab is the

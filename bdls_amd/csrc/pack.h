@@ -123,10 +123,12 @@ inline uint64_t load64(const uint8_t* p) {
 // Equal keys always collide; keys crafted to share these bytes only lengthen
 // probe runs -- past the probe limit the table is rebuilt and then dedup is
 // dropped, so the packed batch stays exact whatever the keys (every match is
-// confirmed on all 64 bytes).
+// confirmed on all KB bytes). KB: the key width, 64 (P-256, secp256k1) or 96
+// (P-384): X || Y of KB / 2 bytes each.
+template <int KB = 64>
 inline uint64_t key_hash(const uint8_t* k) {
   uint64_t h = (load64(k) ^ 0x9E3779B97F4A7C15ull) * 0xff51afd7ed558ccdull;
-  h = (h ^ (h >> 29) ^ load64(k + 32)) * 0xc4ceb9fe1a85ec53ull;
+  h = (h ^ (h >> 29) ^ load64(k + KB / 2)) * 0xc4ceb9fe1a85ec53ull;
   return h ^ (h >> 32);
 }
 
@@ -147,7 +149,7 @@ constexpr uint32_t kBusy = 0xFFFFFFFFu;
 
 // Lock-free insert-or-find. slots: cap (power of two) u64 words, 0 = empty,
 // else tag (hash high word | 1) << 32 | key id (kBusy while the claimant
-// copies its key). keys: the dense key array (64 B per id) the compares read,
+// copies its key). keys: the dense key array (KB bytes per id) the compares read,
 // in ordinary cached memory; keys_out: its copy in the upload staging, only
 // written (page-locked host memory reads back uncached). Returns the key's
 // id, or kBusy when the table is full / the id range exhausted / probing
@@ -159,6 +161,7 @@ constexpr uint32_t kIdBlock = 64;
 struct IdBlock {
   uint32_t next = 0, end = 0, size = kIdBlock;
 };
+template <int KB = 64>
 inline uint32_t insert_key(std::atomic<uint64_t>* slots, uint64_t cap, std::atomic<uint32_t>* next,
                            uint32_t max_ids, uint8_t* keys, uint8_t* keys_out,
                            const uint8_t* key, uint64_t h, IdBlock* blk) {
@@ -178,8 +181,8 @@ inline uint32_t insert_key(std::atomic<uint64_t>* slots, uint64_t cap, std::atom
           slots[p].store(tag | (kBusy - 1), std::memory_order_release);  // never matches a key
           return kBusy;
         }
-        std::memcpy(keys + (size_t)id * 64, key, 64);
-        std::memcpy(keys_out + (size_t)id * 64, key, 64);
+        std::memcpy(keys + (size_t)id * KB, key, KB);
+        std::memcpy(keys_out + (size_t)id * KB, key, KB);
         slots[p].store(tag | id, std::memory_order_release);
         return id;
       }
@@ -191,7 +194,7 @@ inline uint32_t insert_key(std::atomic<uint64_t>* slots, uint64_t cap, std::atom
       std::this_thread::yield();
       id = (uint32_t)slots[p].load(std::memory_order_acquire);
     }
-    if (id < max_ids && std::memcmp(keys + (size_t)id * 64, key, 64) == 0) return id;
+    if (id < max_ids && std::memcmp(keys + (size_t)id * KB, key, KB) == 0) return id;
   }
   return kBusy;
 }
@@ -251,7 +254,7 @@ class StreamWriter {
 
 // ---- the packer ---------------------------------------------------------------
 struct Out {
-  uint8_t* keys = nullptr;      // >= m * 64 bytes
+  uint8_t* keys = nullptr;      // >= m * KB bytes (KB: the packer's key width)
   uint32_t* key_idx = nullptr;  // m (written when Result::dedup)
   uint32_t* sig_len = nullptr;  // m
   uint32_t* msg_len = nullptr;  // m
@@ -281,9 +284,11 @@ struct Result {
 // after chunk c is complete on every thread, on_chunk(c) runs on the calling
 // thread (the H2D of its bytes) while the workers fill chunk c + 1.
 // Src: key(i), sig(i), sig_len(i), msg(i), msg_len(i) for i in [lo, lo + m).
-class Packer {
+// KB: bytes of a key, 64 or 96 (Packer = PackerT<64>; P-384's is PackerT<96>).
+template <int KB>
+class PackerT {
  public:
-  explicit Packer(int threads) : pool_(threads) {}
+  explicit PackerT(int threads) : pool_(threads) {}
   int threads() const { return pool_.threads(); }
 
   template <class Src>
@@ -300,7 +305,7 @@ class Packer {
     } else if (m >= 64) {
       const size_t s = std::min<size_t>(m, 8192);
       std::vector<uint64_t> hs(s);
-      for (size_t k = 0; k < s; k++) hs[k] = key_hash(src.key(lo + (k * m) / s));
+      for (size_t k = 0; k < s; k++) hs[k] = key_hash<KB>(src.key(lo + (k * m) / s));
       std::sort(hs.begin(), hs.end());
       const size_t ds = (size_t)(std::unique(hs.begin(), hs.end()) - hs.begin());
       est = estimate_distinct(s, ds);
@@ -399,7 +404,7 @@ class Packer {
             const uint32_t sl = src.sig_len(i), ml = src.msg_len(i);
             out.sig_len[i - lo] = sl;
             out.msg_len[i - lo] = ml;
-            if (!dedup) std::memcpy(out.keys + (i - lo) * 64, src.key(i), 64);
+            if (!dedup) std::memcpy(out.keys + (i - lo) * KB, src.key(i), KB);
             if (sl) ws.put(src.sig(i), sl);
             if (ml) wm.put(src.msg(i), ml);
           }
@@ -434,7 +439,7 @@ class Packer {
         pool_.run([&](int t) {
           const size_t a = lo + (m * (size_t)t) / T, b = lo + (m * (size_t)(t + 1)) / T;
           for (size_t i = a; i < b; i++) {
-            std::memcpy(out.keys + (i - lo) * 64, src.key(i), 64);
+            std::memcpy(out.keys + (i - lo) * KB, src.key(i), KB);
             out.key_idx[i - lo] = (uint32_t)(i - lo);
           }
         });
@@ -470,7 +475,7 @@ class Packer {
     }
     max_ids_ = (uint32_t)std::min<uint64_t>(cap_ / 2, m);
     if (table_.size() < cap_) table_ = std::vector<std::atomic<uint64_t>>(cap_);
-    if (kcache_.size() < (size_t)max_ids_ * 64) kcache_.resize((size_t)max_ids_ * 64);
+    if (kcache_.size() < (size_t)max_ids_ * KB) kcache_.resize((size_t)max_ids_ * KB);
     pool_.run([&](int t) {  // clear in parallel (the table can be 2 m words)
       const uint64_t a = cap_ * t / pool_.threads(), b = cap_ * (t + 1) / pool_.threads();
       for (uint64_t k = a; k < b; k++) table_[k].store(0, std::memory_order_relaxed);
@@ -493,7 +498,7 @@ class Packer {
     uint32_t cand[kGroup];
     for (int j = 0; j < cnt; j++) {
       kp[j] = src.key(g0 + j);
-      hh[j] = key_hash(kp[j]);
+      hh[j] = key_hash<KB>(kp[j]);
       __builtin_prefetch(&tab[hh[j] & mask]);
     }
     for (int j = 0; j < cnt; j++) {
@@ -502,13 +507,13 @@ class Packer {
       cand[j] = kBusy;
       if ((v >> 32) == ((hh[j] >> 32) | 1u) && id < max_ids_) {
         cand[j] = id;
-        __builtin_prefetch(kc + (size_t)id * 64);
+        __builtin_prefetch(kc + (size_t)id * KB);
       }
     }
     for (int j = 0; j < cnt; j++) {
       uint32_t id = cand[j];
-      if (id == kBusy || std::memcmp(kc + (size_t)id * 64, kp[j], 64) != 0)
-        id = insert_key(tab, cap_, &next_id_, max_ids_, kc, out.keys, kp[j], hh[j], blk);
+      if (id == kBusy || std::memcmp(kc + (size_t)id * KB, kp[j], KB) != 0)
+        id = insert_key<KB>(tab, cap_, &next_id_, max_ids_, kc, out.keys, kp[j], hh[j], blk);
       if (id == kBusy) {
         overflow_.store(true, std::memory_order_relaxed);
         return;
@@ -519,7 +524,7 @@ class Packer {
 
   void zero_holes(const Out& out, const IdBlock& blk) {
     for (uint32_t id = blk.next; id < blk.end && id < max_ids_; id++)
-      std::memset(out.keys + (size_t)id * 64, 0, 64);
+      std::memset(out.keys + (size_t)id * KB, 0, KB);
   }
 
   // the dedup alone over every record (after a table overflow)
@@ -550,6 +555,7 @@ class Packer {
   std::atomic<uint32_t> next_id_{0};
   std::atomic<bool> overflow_{false};
 };
+using Packer = PackerT<64>;
 
 // Worker threads: BH_PACK_THREADS, else the CPUs this process may run on
 // (affinity, and the cgroup v2 quota when there is one) less one for the

@@ -26,8 +26,22 @@ using N384 = Fn_p384;
 constexpr uint32_t F384_HASH_SHA256 = 1u, F384_NO_LOW_S = 2u, F384_HASH_SHA3_256 = 8u;
 constexpr uint8_t ST384_R2OK = 0x80;  // r + n < p: the second x candidate is live
 
+// The distinct keys of an index-keyed pass (In384::key_idx), imported once per
+// shard by keys384_prep (keys384.h), one lane per key: word k of key j's
+// coordinate at qx[k * nks + j], the layout of Work384, so the lanes of the
+// import store side by side and a wave whose records share a few keys gathers
+// a few cache lines per word.
+struct Keys384 {
+  uint32_t nk = 0;           // keys
+  uint32_t nks = 0;          // nk rounded up to 64
+  uint32_t* qx = nullptr;    // 14: Q.x R mod p, canonical
+  uint32_t* qy = nullptr;    // 14
+  uint8_t* st = nullptr;     // [nk] key_import384's verdict: R_OK or R_BAD_KEY
+  uint32_t* slot = nullptr;  // [nk] the key's slot in the registry, or 0xffffffff
+};
+
 struct In384 {  // device pointers (include/bdls_hip.h bh_batch, 96-byte keys)
-  const uint8_t* pub;
+  const uint8_t* pub;  // key_idx == nullptr: record i's key at pub + 96 i; else the kt.nk distinct keys
   const uint8_t* sig;
   const uint64_t* sig_off;
   const uint32_t* sig_len;
@@ -39,7 +53,16 @@ struct In384 {  // device pointers (include/bdls_hip.h bh_batch, 96-byte keys)
   // (digest mode never reads them); nullptr = one span
   const uint64_t* msg2_off = nullptr;
   const uint32_t* msg2_len = nullptr;
+  // index-keyed batches (bh_verify384_compact, bh_batch_verify384_ptrs): record
+  // i's key is key key_idx[i] (< kt.nk) of pub, already imported into kt
+  const uint32_t* key_idx = nullptr;
+  Keys384 kt{};
 };
+
+// The 96 key bytes of record i: the one place that knows the two key layouts.
+BH_HD const uint8_t* in384_key(const In384& in, uint32_t i) {
+  return in.pub + (size_t)(in.key_idx ? in.key_idx[i] : i) * 96;
+}
 
 // Workspace, structure of arrays: word k of record i at base[k * ns + i].
 struct Work384 {
@@ -154,7 +177,19 @@ BH_HD void stage384_prep(const In384& in, const Work384& w, uint32_t i) {
     if (!(in.flags & F384_NO_LOW_S) && (ds.s_big || !w12_geq(half, s))) reason = R_HIGH_S;
   }
   // ---- inside crypto/ecdsa.Verify (verifyNISTEC): Q first, then r, s ranges
-  if (reason == R_OK && !key_import384(in.pub + (size_t)i * 96, qx, qy)) reason = R_BAD_KEY;
+  if (reason == R_OK) {
+    if (in.key_idx) {  // imported once per key: gather the verdict and the coordinates
+      const uint32_t k = in.key_idx[i];
+      if (in.kt.st[k] != R_OK) {
+        reason = R_BAD_KEY;
+      } else {
+        ldw<14>(qx, in.kt.qx, k, in.kt.nks);
+        ldw<14>(qy, in.kt.qy, k, in.kt.nks);
+      }
+    } else if (!key_import384(in384_key(in, i), qx, qy)) {
+      reason = R_BAD_KEY;
+    }
+  }
   if (reason == R_OK && (ds.r_big || w12_geq(r, nn))) reason = R_R_RANGE;
   if (reason == R_OK && (ds.s_big || w12_geq(s, nn))) reason = R_S_RANGE;
   if (reason == R_OK) digest_e384(in, i, e);

@@ -27,6 +27,15 @@
 //   k384_comb_rows    1 lane/comb     63 affine entries, one inversion
 //   k384_comb         1 lane/record   comb route: 64 doublings, u2 Q + u1 G folded
 //   k384_comb_g       1 lane          the comb of G, once per device
+//
+// An index-keyed shard (In384::key_idx: bh_verify384_compact,
+// bh_batch_verify384_ptrs) imports its distinct keys once, ahead of its chunks:
+//   k384_keys_prep        1 lane/key      key_import384, registry lookup -> Keys384
+// k384_prep then gathers verdict and coordinates, k384_plan reads the key's
+// slot, and a flagged pass groups by key index:
+//   k384_comb_group_idx   1 lane/record   one atomic addition on cnt[key_idx[i]]
+//   k384_comb_assign_idx  1 lane/key      registry, comb slot or ladder
+//   k384_comb_bases_idx   1 lane/comb     the chain from the key workspace
 #include "comb384.h"
 
 using namespace bh;
@@ -157,7 +166,7 @@ __global__ __launch_bounds__(64) void k384_comb_group(In384 in, Work384 w, Comb3
   if (i >= n) return;
   uint32_t b = kNoSlot384;
   if ((w.st[i] & 0x7fu) == R_OK) {
-    b = comb384_claim(in.pub, cb, i, Cas384{});
+    b = comb384_claim(in, cb, i, Cas384{});
     if (b != kNoSlot384) atomicAdd(&cb.cnt[b], 1u);
   }
   cb.bkt[i] = b;
@@ -168,13 +177,58 @@ __global__ __launch_bounds__(64) void k384_comb_assign(In384 in, KeyReg384 g, Co
   if (i >= n) return;
   const uint32_t b = cb.bkt[i];
   if (b == kNoSlot384 || cb.rep[b] != i + 1) return;
-  uint32_t r = comb384_group_route(in.pub, g, cb, i, b);
+  uint32_t r = comb384_group_route(in, g, cb, i, b);
   if (r == 0) {
     r = atomicAdd(&cb.ctr[0], 1u);
     if (r < cb.cap) cb.slot_rep[r] = i;
     else r = kNoSlot384;  // (cap >= ns / min: not reached)
   }
   cb.gslot[b] = r;
+}
+
+__global__ __launch_bounds__(64) void k384_keys_prep(const uint8_t* __restrict__ pub, Keys384 kt,
+                                                     KeyReg384 g) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= kt.nk) return;
+  keys384_prep(pub, kt, g, j);
+}
+
+// The 64 records of a wave mostly share a few keys: the additions of one
+// address are combined by the hardware's atomic unit in L2, one instruction
+// per lane, no loop over the wave.
+__global__ __launch_bounds__(64) void k384_comb_group_idx(In384 in, Work384 w, Comb384 cb,
+                                                          uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t b = kNoSlot384;
+  if ((w.st[i] & 0x7fu) == R_OK) {
+    b = in.key_idx[i];
+    atomicAdd(&cb.cnt[b], 1u);
+  }
+  cb.bkt[i] = b;
+}
+
+__global__ __launch_bounds__(64) void k384_comb_assign_idx(In384 in, Comb384 cb) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= in.kt.nk) return;
+  uint32_t r = comb384_index_route(in.kt, cb, j);
+  if (r == 0) {
+    r = atomicAdd(&cb.ctr[0], 1u);
+    if (r < cb.cap) cb.slot_rep[r] = j;
+    else r = kNoSlot384;  // (cap >= ns / min: not reached)
+  }
+  cb.gslot[j] = r;
+}
+
+__global__ __launch_bounds__(64) void k384_comb_bases_idx(In384 in, Comb384 cb) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t ns = cb.ctr[0] < cb.cap ? cb.ctr[0] : cb.cap;
+  if (t >= ns) return;
+  const uint32_t j = cb.slot_rep[t];
+  uint32_t qx[14], qy[14];
+  ldw<14>(qx, in.kt.qx, j, in.kt.nks);
+  ldw<14>(qy, in.kt.qy, j, in.kt.nks);
+  comb384_bases(qx, qy, cb.bases + (size_t)t * kComb384BaseWords);
 }
 
 __global__ __launch_bounds__(64) void k384_comb_plan(Comb384 cb, uint32_t n, Plan384 pl) {
@@ -347,13 +401,19 @@ hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg
   const uint32_t stride = (n + kInvChunk384 - 1) / kInvChunk384;
   hipLaunchKernelGGL(k384_inv, dim3((stride + 63) / 64), blk, 0, s, w, stride, n);
   if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_comb_group, grd, blk, 0, s, in, w, cb, n);
-  hipLaunchKernelGGL(k384_comb_assign, grd, blk, 0, s, in, g, cb, n);
+  if (in.key_idx) {  // grouped by key index (cb.hc >= in.kt.nk)
+    hipLaunchKernelGGL(k384_comb_group_idx, grd, blk, 0, s, in, w, cb, n);
+    hipLaunchKernelGGL(k384_comb_assign_idx, dim3((in.kt.nk + 63) / 64), blk, 0, s, in, cb);
+  } else {
+    hipLaunchKernelGGL(k384_comb_group, grd, blk, 0, s, in, w, cb, n);
+    hipLaunchKernelGGL(k384_comb_assign, grd, blk, 0, s, in, g, cb, n);
+  }
   hipLaunchKernelGGL(k384_comb_plan, grd, blk, 0, s, cb, n, pl);
   if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
   if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
   if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_comb_bases, grdk, blk, 0, aux, w, cb);
+  if (in.key_idx) hipLaunchKernelGGL(k384_comb_bases_idx, grdk, blk, 0, aux, in, cb);
+  else hipLaunchKernelGGL(k384_comb_bases, grdk, blk, 0, aux, w, cb);
   hipLaunchKernelGGL(k384_comb_rows, grdk, blk, 0, aux, cb);
   if (ev && (e = hipEventRecord(ev[7], aux)) != hipSuccess) return e;
   hipLaunchKernelGGL(k384_comb, grd, blk, 0, aux, w, cb, pl, gcomb, reason);
@@ -365,6 +425,15 @@ hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg
   if ((e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
   hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
   if (ev && (e = hipEventRecord(ev[6], s)) != hipSuccess) return e;
+  return hipGetLastError();
+}
+
+// The distinct keys of an index-keyed shard (kt.nk of them at pub, device) into
+// the key workspace kt, once per shard; g.cap == 0: no registry lookup.
+hipError_t launch_keys384_prep(const uint8_t* pub, const Keys384& kt, const KeyReg384& g,
+                               hipStream_t s) {
+  if (kt.nk == 0) return hipSuccess;
+  hipLaunchKernelGGL(k384_keys_prep, dim3((kt.nk + 63) / 64), dim3(64), 0, s, pub, kt, g);
   return hipGetLastError();
 }
 

@@ -148,7 +148,9 @@ extern "C" {
                            >= 1: the leftmost 48 bytes, a shorter digest whole, one reduction
                            mod n. BH_F_KEEP_KEYS and BH_F_ANY_LANE are ignored; BH_F_BATCH_KEYS
                            gives keys repeated within a pass a comb for that pass. Every other
-                           entry point answers BH_E_INVALID for this curve. */
+                           entry point with a curve argument answers BH_E_INVALID for this curve;
+                           the compact and the staged BatchVerify for it are entry points of
+                           their own (bh_verify384_compact, bh_batch_verify384_ptrs). */
 
 /* Bytes of one public key (X || Y) in bh_batch.pub for a curve: 64, 64, 96;
  * negative for an unknown curve. */
@@ -372,6 +374,54 @@ int bh_batch_verify_ptrs_submit(int curve, const bh_pbatch *b, size_t n, uint32_
  * rebuilds, [9] staged shards since start. Not in the reference
  * (operations metrics). */
 int bh_pack_stats(double out[10]);
+
+/* ---- P-384 BatchVerify: compact keys, job handles, every device ---------------
+ * The compact and the staged BatchVerify for ECDSA P-384 keys. Replaces
+ * BatchVerify over bccsp/sw/impl.go:247-270 and bccsp/sw/ecdsa.go:41-57 for
+ * P-384 keys, and the batch points in common/policies/policy.go:363-395, as
+ * bh_verify_compact and bh_batch_verify_ptrs do for P-256 (which keep refusing
+ * BH_CURVE_P384: these entry points are P-384's own).
+ * Results are, bit for bit, those of bh_verify(BH_CURVE_P384) on the expanded
+ * batch. Flags: BH_F_HASH_SHA256, BH_F_HASH_SHA3_256, BH_F_NO_LOW_S and
+ * BH_F_BATCH_KEYS; BH_F_KEEP_KEYS and BH_F_ANY_LANE are ignored, as everywhere
+ * for this curve; BH_F_HASH_SHA384 / BH_F_HASH_SHA512 are refused (BH_E_INVALID:
+ * use bh_verify). BH_E_INVALID also for a key index >= nkeys, a null required
+ * field and n > 2^32 - 1; BH_E_NOT_INIT before bh_init (argument checks come
+ * first). n = 0 is BH_OK; a submit form still returns a job to wait.
+ * The batch is dealt over all initialised devices in 64-aligned shards
+ * (BH_HOST_SHARDS per device, read once); a device runs a shard in passes of
+ * BH_P384_CHUNK records. Each device has two pipeline slots: a shard is copied
+ * into page-locked staging the library reuses, uploaded on the copy stream and
+ * verified behind the device's earlier P-384 work, so one job's upload runs
+ * under another's kernels and the submit forms return once everything is
+ * enqueued (a call waits only for a slot that still holds an uncollected shard,
+ * or where a buffer has to grow). Jobs are collected with bh_verify_wait,
+ * exactly once each, in any order, P-256 jobs among them. bh_device_stats
+ * counts one batch per call, however many shards and chunks.
+ * Keys are imported (range and curve checks, Montgomery form) and looked up in
+ * the bh_keys384_* registry once per distinct key of a shard, not once per
+ * record. With BH_F_BATCH_KEYS a pass counts its records per key INDEX (keys of
+ * >= BH_P384_COMB_MIN records, default 4, get a comb for that pass): two
+ * indices whose 96 bytes happen to be equal count as two keys. Results never
+ * depend on that. key_idx = NULL selects the per-record key layout and the
+ * grouping by key bytes bh_verify uses.
+ *
+ * bh_verify384_compact: bh_cbatch as documented with keys of 96 bytes (X || Y,
+ * 48 each), keys = nkeys * 96. A shard uploads only the keys its records use.
+ * The inputs are copied when the submit call returns. */
+int bh_verify384_compact(const bh_cbatch *b, size_t n, uint32_t flags, uint8_t *bitmap,
+                         uint8_t *reason);
+int bh_verify384_compact_submit(const bh_cbatch *b, size_t n, uint32_t flags, uint8_t *bitmap,
+                                uint8_t *reason, bh_job **job);
+/* The staged form from the caller's own per-record buffers: bh_pbatch with
+ * 96-byte keys. The library de-duplicates keys by content (pack.h at key
+ * width 96) and packs into the slot's page-locked staging; NULL sig / msg /
+ * key pointers mean what they mean for bh_batch_verify_ptrs. The caller's
+ * buffers may be released when the submit call returns. */
+int bh_batch_verify384_ptrs(const bh_pbatch *b, size_t n, uint32_t flags, uint8_t *bitmap,
+                            uint8_t *reason);
+int bh_batch_verify384_ptrs_submit(const bh_pbatch *b, size_t n, uint32_t flags, uint8_t *bitmap,
+                                   uint8_t *reason, bh_job **job);
 
 /* Device batches since bh_init over every entry point: out[0] batches launched
  * (one per device pass sequence of a call or shard, one per latency-path
