@@ -13,7 +13,8 @@ all: $(LIB)/libbdlship.so $(LIB)/libbdlsgen.so oracle tests/native/build/libhost
      tests/native/build/libhostsim384.so tests/native/build/libhostsim384k.so \
      tests/native/build/libhostsim384s.so tests/native/build/libhostsim512.so \
      tests/native/build/libhostsimfused.so tests/native/build/libhostsim384c.so \
-     tests/native/build/libhostsimlltab.so tests/native/build/libhostsim384i.so $(LIB)/csp_load
+     tests/native/build/libhostsimlltab.so tests/native/build/libhostsim384i.so \
+     tests/native/build/libhostsimhash.so $(LIB)/csp_load
 
 $(LIB)/verify_kernels.o: $(CSRC)/verify_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
@@ -26,6 +27,11 @@ $(LIB)/verify384_kernels.o: $(CSRC)/verify384_kernels.hip $(HDRS)
 
 # the SHA-384 / SHA-512 digest pre-pass (BH_F_HASH_SHA384 / _SHA512): its own unit too
 $(LIB)/sha512_kernels.o: $(CSRC)/sha512_kernels.hip $(HDRS)
+	@mkdir -p $(LIB)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# bh_hash: SHA-256 / SHA3-256 over span records, digests or comparisons out: its own unit too
+$(LIB)/hash_kernels.o: $(CSRC)/hash_kernels.hip $(HDRS)
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -42,7 +48,7 @@ $(LIB)/fabric.o: $(CSRC)/fabric.cpp $(HDRS)
 	g++ -O2 -std=c++17 -fPIC -Wall -Wno-unknown-pragmas -c $< -o $@
 
 $(LIB)/libbdlship.so: $(LIB)/verify_kernels.o $(LIB)/verify384_kernels.o $(LIB)/sha512_kernels.o \
-                     $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o
+                     $(LIB)/hash_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o $(LIB)/fabric.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 $(LIB)/libbdlsgen.so: bdls_amd/workload/gen.c
@@ -100,6 +106,11 @@ tests/native/build/libhostsim512.so: tests/native_sha512/hostsim_sha512.cpp $(HD
 	@mkdir -p tests/native/build
 	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
 
+# hashspan.h's span loaders and compare step (bh_hash's kernels) on their own
+tests/native/build/libhostsimhash.so: tests/native_hash/hostsim_hash.cpp $(HDRS)
+	@mkdir -p tests/native/build
+	$(CLANGXX) -O2 -std=c++17 -shared -fPIC -o $@ $<
+
 # the fused field / point formulas (f_mul2, j_zaddc, the composite 2A + T) on their own
 tests/native/build/libhostsimfused.so: tests/native_fused/hostsim_fused.cpp $(HDRS)
 	@mkdir -p tests/native/build
@@ -139,7 +150,8 @@ exp:
 	@for v in $(EXP_VARIANTS); do n=$${v%%:*}; f=$$(echo $${v#*:} | tr '+' ' '); \
 	  $(HIPCC) $(HIPFLAGS) $$f -c $(CSRC)/verify_kernels.hip -o build/exp/vk_$$n.o && \
 	  $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/exp/libbdlship_$$n.so build/exp/vk_$$n.o \
-	    $(LIB)/verify384_kernels.o $(LIB)/sha512_kernels.o $(LIB)/bdls_hip.o $(LIB)/bdls_msg.o \
+	    $(LIB)/verify384_kernels.o $(LIB)/sha512_kernels.o $(LIB)/hash_kernels.o $(LIB)/bdls_hip.o \
+    $(LIB)/bdls_msg.o \
 	    $(LIB)/fabric.o -lpthread || exit 1; done
 
 clean:

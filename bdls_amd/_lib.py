@@ -25,6 +25,14 @@ BH_F_BATCH_KEYS = 128
 BH_CURVE_P256 = 0
 BH_CURVE_SECP256K1 = 1
 BH_CURVE_P384 = 2
+BH_E_INVALID = -1
+BH_HASH_SHA256 = 1
+BH_HASH_SHA3_256 = 2
+BH_HASH_WANT_RAW = 0
+BH_HASH_WANT_HEX = 1
+BH_HASH_MATCH = 0
+BH_HASH_MISMATCH = 1
+BH_HASH_RANGE = 2
 
 # Every symbol include/bdls_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -45,6 +53,7 @@ EXPORTS = (
     "bh_verify_mixed",
     "bh_verify384_compact", "bh_verify384_compact_submit", "bh_batch_verify384_ptrs",
     "bh_batch_verify384_ptrs_submit",
+    "bh_hash", "bh_hash_submit", "bh_hash_dev", "bh_fabric_block_prevalidate",
 )
 KEY_FULL = 255  # bh_keys_register / bh_keys384_register status: registry full
 
@@ -130,6 +139,23 @@ class BhFabSigref(ctypes.Structure):
                 ("reason", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class BhHBatch(ctypes.Structure):
+    """include/bdls_hip.h bh_hbatch: records of up to three spans of one buffer."""
+    _fields_ = [("data", ctypes.c_void_p), ("data_len", ctypes.c_size_t),
+                ("off", ctypes.c_void_p), ("len", ctypes.c_void_p), ("nspan", ctypes.c_uint32),
+                ("want_off", ctypes.c_void_p), ("want_len", ctypes.c_void_p),
+                ("want_kind", ctypes.c_void_p)]
+
+
+class BhFabTxhash(ctypes.Structure):
+    """include/bdls_hip.h bh_fab_txhash."""
+    SPANS = ("nonce", "creator", "txid", "chdr", "ashdr", "ccpp", "phash")
+    _fields_ = ([("txid", ctypes.c_uint8), ("proposal_hash", ctypes.c_uint8),
+                 ("reserved", ctypes.c_uint8 * 6)]
+                + [(f"{s}_off", ctypes.c_uint64) for s in SPANS]
+                + [(f"{s}_len", ctypes.c_uint32) for s in SPANS] + [("pad", ctypes.c_uint32)])
+
+
 class BhSdBatch(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in
                 ("identity", "identity_off", "identity_len", "data", "data_off", "data_len",
@@ -145,6 +171,9 @@ BH_FAB_F_SHA3 = 1
 BH_FAB_F_KEEP_KEYS = 2
 BH_FAB_F_DECODE_ONLY = 4
 BH_BLK_F_BFT = 8
+BH_FAB_TXID = 8
+BH_FAB_PROPOSAL_HASH = 9
+BH_FAB_H_NOT_CHECKED = 0xFF
 
 
 class BhConsenterSet(ctypes.Structure):
@@ -243,6 +272,21 @@ def lib() -> ctypes.CDLL:
                                                      sz, ctypes.POINTER(sz), vp, sz,
                                                      ctypes.POINTER(sz)]
         L.bh_fabric_block_preverify_refs.restype = i32
+        try:  # (an A/B run may load a library built before these entry points; a caller
+            # of a missing one still gets ctypes' AttributeError)
+            L.bh_fabric_block_prevalidate.argtypes = [vp, sz, u32, vp, sz, ctypes.POINTER(sz), vp,
+                                                      sz, ctypes.POINTER(sz), vp, sz,
+                                                      ctypes.POINTER(sz), vp]
+            L.bh_fabric_block_prevalidate.restype = i32
+            L.bh_hash.argtypes = [i32, ctypes.POINTER(BhHBatch), sz, vp, vp]
+            L.bh_hash.restype = i32
+            L.bh_hash_submit.argtypes = [i32, ctypes.POINTER(BhHBatch), sz, vp, vp,
+                                         ctypes.POINTER(vp)]
+            L.bh_hash_submit.restype = i32
+            L.bh_hash_dev.argtypes = [i32, i32, ctypes.POINTER(BhHBatch), sz, vp, vp, vp, i32]
+            L.bh_hash_dev.restype = i32
+        except AttributeError:
+            pass
         L.bh_signature_sets_verify.argtypes = [ctypes.POINTER(BhSdBatch), sz, vp, sz, u32, vp, vp]
         L.bh_signature_sets_verify.restype = i32
         L.bh_envelopes_preverify.argtypes = [vp, vp, vp, sz, u32, vp, vp]

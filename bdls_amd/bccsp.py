@@ -260,6 +260,26 @@ class HipCSP:
             return hashlib.sha384(msg).digest()
         return hashlib.sha256(msg).digest()
 
+    # -- BCCSP.Hash as a batch (bccsp/bccsp.go:109, bccsp/sw/impl.go:177-194): the
+    # messages hashed on the device in one bh_hash call. SHA2-256 (the default
+    # opts) and SHA3-256; the wider digests are not offered by bh_hash.
+    def batch_hash(self, msgs: Sequence[bytes], opts=None) -> list[bytes]:
+        if isinstance(opts, SHA384Opts):
+            raise BCCSPError(-1, f"Unsupported 'HashOpt' provided [{opts}]")
+        alg = _lib.BH_HASH_SHA3_256 if isinstance(opts, SHA3_256Opts) else _lib.BH_HASH_SHA256
+        n = len(msgs)
+        if n == 0:
+            return []
+        ln = np.array([len(m) for m in msgs], np.uint32)
+        off = np.zeros(n, np.uint64)
+        off[1:] = np.cumsum(ln[:-1], dtype=np.uint64)
+        data = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\0", np.uint8)
+        out = np.zeros(n * 32, np.uint8)
+        b = _lib.BhHBatch(data.ctypes.data, len(data) - 1, off.ctypes.data, ln.ctypes.data, 1,
+                          None, None, None)
+        _lib.check(_lib.lib().bh_hash(alg, ctypes.byref(b), n, out.ctypes.data, None))
+        return [out[32 * i:32 * i + 32].tobytes() for i in range(n)]
+
     def key_import(self, raw, opts) -> ECDSAPublicKey:
         if isinstance(opts, ECDSAGoPublicKeyImportOpts):
             x, y = raw

@@ -33,6 +33,7 @@
 #include "verify384.h"
 #include "pack.h"
 #include "shard.h"
+#include "hashspan.h"
 
 namespace bh {
 hipError_t launch_gtab_build(int curve, uint32_t* gtab, hipStream_t s);
@@ -71,6 +72,8 @@ hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* g
                             uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev);
 size_t expand_temp_bytes(uint32_t m);
 hipError_t launch_result_out(const void* src, void* host_dst, size_t bytes, hipStream_t s);
+hipError_t launch_hash(int alg, const HashIn& in, uint32_t n, uint8_t* digest, uint8_t* result,
+                       hipStream_t s);
 hipError_t launch_expand(const uint8_t* keys, const uint32_t* key_idx, uint8_t* pub,
                          const uint32_t* sig_len, uint64_t* sig_off, const uint32_t* msg_len,
                          uint64_t* msg_off, uint32_t* msg_len_out, uint32_t stride, void* temp,
@@ -235,6 +238,21 @@ struct Slot384 {
 };
 constexpr int kSlots384 = 2;
 
+// One of a device's two bh_hash slots: the batch's arrays packed into
+// page-locked staging, their device copy with the uploaded data bytes behind
+// them, digests and results on the device and in page-locked memory, and the
+// event that ends the job. Everything runs on the device's hash stream.
+struct HashSlot {
+  HostBuf hin;
+  DevBuf din;
+  DevBuf dout;
+  HostBuf hout{nullptr, 0, hipHostMallocPortable | hipHostMallocCoherent};
+  hipEvent_t done = nullptr;
+  bh_job* owner = nullptr;  // job whose results are in flight / sit in hout
+  size_t owner_part = 0;
+};
+constexpr int kHashSlots = 2;
+
 // The extra compute lanes of a device (round 3: one; round 4: up to
 // kMaxLanes - 1). Host-API batches rotate over lane 0 (Dev::stream / aux / ws)
 // and lanes 1.., each with its own workspace, so batch k+1's kernels run beside
@@ -275,6 +293,10 @@ struct Dev {
   // BH_F_HASH_SHA384 / BH_F_HASH_SHA512 (allocated at the device's first such call, under mu)
   DevBuf dig512;  // one chunk's digests, offsets and lengths: the curve pass's digest batch
   hipEvent_t ev512[2] = {nullptr, nullptr};
+  // bh_hash (made at the device's first hash call, under mu)
+  hipStream_t hstream = nullptr;  // hash jobs: beside the compute lanes, not behind them
+  HashSlot hslot[kHashSlots];
+  uint32_t next_hslot = 0;
   DevBuf ws;     // Work + Plan
   DevBuf stage;  // key registration input
   DevBuf out;    // key registration status
@@ -601,6 +623,17 @@ void dev_free(Dev& d) {
     if (sl.done) (void)hipEventDestroy(sl.done);
     sl.uploaded = sl.done = nullptr;
   }
+  if (d.hstream) (void)hipStreamSynchronize(d.hstream);
+  for (HashSlot& sl : d.hslot) {
+    sl.hin.release();
+    sl.din.release();
+    sl.dout.release();
+    sl.hout.release();
+    if (sl.done) (void)hipEventDestroy(sl.done);
+    sl.done = nullptr;
+  }
+  if (d.hstream) (void)hipStreamDestroy(d.hstream);
+  d.hstream = nullptr;
   d.dig512.release();
   for (auto& e : d.ev512) {
     if (e) (void)hipEventDestroy(e);
@@ -974,6 +1007,17 @@ const uint8_t* prestaged_span(int dev, const uint8_t* base, uint64_t lo, uint64_
     return nullptr;
   return (const uint8_t*)m.buf.p;
 }
+// the same for a consumer on another stream than the copy stream (bh_hash):
+// *ev is the event that ends the mirror's H2D
+const uint8_t* prestaged_data(int dev, const uint8_t* base, uint64_t bytes, hipEvent_t* ev) {
+  Mirror& m = mirror();
+  std::lock_guard<std::mutex> g(m.mu);
+  if (!m.busy || !m.issued || m.err != hipSuccess || m.src != base || m.dev != dev ||
+      bytes > m.len || !m.done)
+    return nullptr;
+  *ev = m.done;
+  return (const uint8_t*)m.buf.p;
+}
 
 struct HostFields {
   std::vector<VarField> var;
@@ -1211,6 +1255,7 @@ struct Part {
   bool done;
   bool small = false;  // latency path: reasons only (bitmap formed here)
   bool p384 = false;   // slot indexes Dev::s384 (a P-384 shard), not Dev::slot
+  bool hash = false;   // slot indexes Dev::hslot (a bh_hash job)
 };
 
 }  // namespace
@@ -1220,6 +1265,8 @@ struct bh_job {
   std::vector<Part> parts;
   uint8_t* bitmap = nullptr;
   uint8_t* reason = nullptr;
+  uint8_t* digest = nullptr;   // bh_hash jobs: n * 32 or NULL
+  uint8_t* hresult = nullptr;  // bh_hash jobs: n or NULL
   size_t n = 0;
   int rc = BH_OK;
   std::string err;
@@ -1232,6 +1279,19 @@ int finish_part(bh_job* j, size_t k) {
   Part& p = j->parts[k];
   if (p.done) return BH_OK;
   Dev& d = *p.d;
+  if (p.hash) {
+    HashSlot& hs = d.hslot[p.slot];
+    p.done = true;
+    hs.owner = nullptr;
+    HIPCHK(hipSetDevice(d.id));
+    hipError_t eh = hipEventSynchronize(hs.done);
+    if (eh != hipSuccess)
+      return fail(BH_E_DEVICE, std::string("hash pass failed: ") + hipGetErrorString(eh));
+    const uint8_t* o = (const uint8_t*)hs.hout.p;
+    if (j->digest) std::memcpy(j->digest, o, p.m * 32);
+    if (j->hresult) std::memcpy(j->hresult, o + round256(p.m * 32), p.m);
+    return BH_OK;
+  }
   if (p.p384) {
     Slot384& s3 = d.s384[p.slot];
     p.done = true;
@@ -1684,7 +1744,9 @@ int wait_job(bh_job* j) {
     {
       std::lock_guard<std::mutex> g(d.mu);
       const Part& pk = j->parts[k];
-      if (!pk.done) ev = pk.p384 ? d.s384[pk.slot].done : d.slot[pk.slot].done;
+      if (!pk.done)
+        ev = pk.hash ? d.hslot[pk.slot].done
+                     : pk.p384 ? d.s384[pk.slot].done : d.slot[pk.slot].done;
     }
     if (ev) {
       // no early return: every part is still collected (finish_part releases
@@ -2591,6 +2653,153 @@ int submit384(size_t n, uint8_t* bitmap, uint8_t* reason, bh_job** out, Enq enq)
 }
 
 // device >= 0: that device; -1: every initialised device.
+// ---- bh_hash ------------------------------------------------------------------
+int hash_setup(Dev& d) {
+  if (d.hstream) return BH_OK;
+  HIPCHK(hipStreamCreateWithFlags(&d.hstream, hipStreamNonBlocking));
+  for (HashSlot& sl : d.hslot)
+    HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming |
+                                                 (blocking_sync() ? hipEventBlockingSync : 0u)));
+  return BH_OK;
+}
+
+// The argument checks of every bh_hash form (host: the arrays are readable).
+int check_hash(int alg, const bh_hbatch* b, size_t n, const uint8_t* digest,
+               const uint8_t* result, bool host) {
+  if (alg != BH_HASH_SHA256 && alg != BH_HASH_SHA3_256)
+    return fail(BH_E_INVALID, "bh_hash: alg must be BH_HASH_SHA256 or BH_HASH_SHA3_256 (SHA-384, "
+                              "SHA-512 and SHA3-384 are not offered)");
+  if (!b) return fail(BH_E_INVALID, "bh_hash: null batch");
+  if (b->nspan < 1 || b->nspan > bh::kHashMaxSpans)
+    return fail(BH_E_INVALID, "bh_hash: nspan must be 1..3");
+  if (n > 0xffffffffull) return fail(BH_E_INVALID, "bh_hash: batch too large");
+  if (n == 0) return BH_OK;
+  if (!b->data || !b->off || !b->len) return fail(BH_E_INVALID, "bh_hash: null data / off / len");
+  if (!digest && !result) return fail(BH_E_INVALID, "bh_hash: digest and result both null");
+  const int wn = (b->want_off != nullptr) + (b->want_len != nullptr) + (b->want_kind != nullptr);
+  if (wn != 0 && wn != 3)
+    return fail(BH_E_INVALID, "bh_hash: want_off / want_len / want_kind must all be set or all "
+                              "be null");
+  if (result && wn == 0) return fail(BH_E_INVALID, "bh_hash: result needs want_*");
+  if (!host) return BH_OK;
+  for (size_t k = 0; k < n * b->nspan; k++)
+    if (!bh::hs_in_range(b->off[k], b->len[k], b->data_len))
+      return fail(BH_E_INVALID, "bh_hash: record " + std::to_string(k / b->nspan) + " span " +
+                                    std::to_string(k % b->nspan) + " ends beyond data_len");
+  if (wn)
+    for (size_t i = 0; i < n; i++)
+      if (!bh::hs_in_range(b->want_off[i], b->want_len[i], b->data_len))
+        return fail(BH_E_INVALID, "bh_hash: record " + std::to_string(i) +
+                                      " expected span ends beyond data_len");
+  return BH_OK;
+}
+
+// Enqueue the whole (checked) batch on device d's hash stream (caller holds d.mu).
+int enqueue_hash(bh_job* j, Dev& d, int alg, const bh_hbatch* b, size_t n) {
+  HIPCHK(hipSetDevice(d.id));
+  int rc;
+  if ((rc = hash_setup(d))) return rc;
+  const int k = (int)(d.next_hslot++ % kHashSlots);
+  HashSlot& sl = d.hslot[k];
+  if (sl.owner) {  // the slot still holds an uncollected job: collect it now
+    bh_job* o = sl.owner;
+    rc = finish_part(o, sl.owner_part);
+    if (rc && o->rc == BH_OK) {
+      o->rc = rc;
+      o->err = g_err;
+    }
+  }
+  hipStream_t s = d.hstream;
+  const bool want = b->want_off != nullptr;
+  const size_t ns = n * b->nspan;
+  const size_t o_len = round256(ns * 8), o_woff = o_len + round256(ns * 4),
+               o_wlen = o_woff + round256(want ? n * 8 : 0),
+               o_wkind = o_wlen + round256(want ? n * 4 : 0),
+               small = o_wkind + round256(want ? n : 0);
+  // the bytes the records cover: [lo, hi) of data
+  uint64_t lo = UINT64_MAX, hi = 0;
+  auto cover = [&](uint64_t off, uint32_t len) {
+    if (!len) return;
+    lo = std::min(lo, off);
+    hi = std::max(hi, off + len);
+  };
+  for (size_t q = 0; q < ns; q++) cover(b->off[q], b->len[q]);
+  if (want)
+    for (size_t i = 0; i < n; i++) cover(b->want_off[i], b->want_len[i]);
+  if (hi <= lo) lo = hi = 0;
+  hipEvent_t mev = nullptr;
+  const uint8_t* pre = prestaged_data(d.id, b->data, b->data_len, &mev);
+  if ((rc = sl.hin.ensure(small))) return rc;
+  if ((rc = sl.din.ensure(small + (pre ? 0 : (size_t)(hi - lo)) + 4096))) return rc;
+  const size_t o_res = round256(n * 32), out_bytes = o_res + round256(n);
+  if ((rc = sl.dout.ensure(out_bytes))) return rc;
+  if ((rc = sl.hout.ensure(out_bytes))) return rc;
+  char* h = (char*)sl.hin.p;
+  std::memcpy(h, b->off, ns * 8);
+  std::memcpy(h + o_len, b->len, ns * 4);
+  if (want) {
+    std::memcpy(h + o_woff, b->want_off, n * 8);
+    std::memcpy(h + o_wlen, b->want_len, n * 4);
+    std::memcpy(h + o_wkind, b->want_kind, n);
+  }
+  char* dv = (char*)sl.din.p;
+  HIPCHK(hipMemcpyAsync(dv, h, small, hipMemcpyHostToDevice, s));
+  const uint8_t* ddata;
+  if (pre) {  // the block is on the device already (or queued on the copy stream)
+    HIPCHK(hipStreamWaitEvent(s, mev, 0));
+    ddata = pre;
+  } else {
+    if (hi > lo)
+      HIPCHK(hipMemcpyAsync(dv + small, b->data + lo, hi - lo, hipMemcpyHostToDevice, s));
+    ddata = (const uint8_t*)(dv + small) - lo;  // the caller's offsets index it directly
+  }
+  bh::HashIn in{ddata, b->data_len, (const uint64_t*)dv, (const uint32_t*)(dv + o_len), b->nspan,
+                want ? (const uint64_t*)(dv + o_woff) : nullptr,
+                want ? (const uint32_t*)(dv + o_wlen) : nullptr,
+                want ? (const uint8_t*)(dv + o_wkind) : nullptr};
+  uint8_t* ddig = j->digest ? (uint8_t*)sl.dout.p : nullptr;
+  uint8_t* dres = j->hresult ? (uint8_t*)sl.dout.p + o_res : nullptr;
+  g_dev_batches.fetch_add(1, std::memory_order_relaxed);
+  g_dev_records.fetch_add(n, std::memory_order_relaxed);
+  HIPCHK(bh::launch_hash(alg, in, (uint32_t)n, ddig, dres, s));
+  if (ddig) HIPCHK(bh::launch_result_out(ddig, sl.hout.p, n * 32, s));
+  if (dres) HIPCHK(bh::launch_result_out(dres, (uint8_t*)sl.hout.p + o_res, n, s));
+  HIPCHK(hipEventRecord(sl.done, s));
+  sl.owner = j;
+  sl.owner_part = j->parts.size();
+  Part part{&d, k, 0, n, false};
+  part.hash = true;
+  j->parts.push_back(part);
+  return BH_OK;
+}
+
+int submit_hash(int alg, const bh_hbatch* b, size_t n, uint8_t* digest, uint8_t* result,
+                bh_job** out) {
+  *out = nullptr;
+  if (int rc = check_hash(alg, b, n, digest, result, true)) return rc;
+  std::vector<Dev*> devs = all_devs();
+  if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
+  bh_job* j = new bh_job();
+  j->digest = digest;
+  j->hresult = result;
+  j->n = n;
+  if (n) {
+    Dev& d = *devs[0];
+    int rc;
+    {
+      std::lock_guard<std::mutex> g(d.mu);
+      rc = enqueue_hash(j, d, alg, b, n);
+    }
+    if (rc) {
+      const std::string err = g_err;
+      (void)wait_job(j);  // drain what was enqueued
+      return fail(rc, err);
+    }
+  }
+  *out = j;
+  return BH_OK;
+}
+
 int for_devices(int device, const std::function<int(Dev&)>& fn) {
   std::vector<Dev*> ds;
   if (device < 0) {
@@ -3346,6 +3555,37 @@ int bh_batch_verify384_ptrs(const bh_pbatch* b, size_t n, uint32_t flags, uint8_
   bh_job* j = nullptr;
   if (int rc = bh_batch_verify384_ptrs_submit(b, n, flags, bitmap, reason, &j)) return rc;
   return wait_job(j);
+}
+
+int bh_hash_submit(int alg, const bh_hbatch* b, size_t n, uint8_t* digest, uint8_t* result,
+                   bh_job** job) {
+  if (!job) return fail(BH_E_INVALID, "null job pointer");
+  return submit_hash(alg, b, n, digest, result, job);
+}
+
+int bh_hash(int alg, const bh_hbatch* b, size_t n, uint8_t* digest, uint8_t* result) {
+  bh_job* j = nullptr;
+  if (int rc = submit_hash(alg, b, n, digest, result, &j)) return rc;
+  return wait_job(j);
+}
+
+int bh_hash_dev(int device, int alg, const bh_hbatch* b, size_t n, uint8_t* digest,
+                uint8_t* result, void* stream, int sync) {
+  if (int rc = check_hash(alg, b, n, digest, result, false)) return rc;
+  Dev* d = get_dev(device);
+  if (!d) return fail(BH_E_NOT_INIT, "device not initialised (call bh_init)");
+  if (n == 0) return BH_OK;
+  std::lock_guard<std::mutex> g(d->mu);
+  HIPCHK(hipSetDevice(d->id));
+  if (int rc = hash_setup(*d)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : d->hstream;
+  const bh::HashIn in{b->data, b->data_len, b->off, b->len, b->nspan,
+                      b->want_off, b->want_len, b->want_kind};
+  g_dev_batches.fetch_add(1, std::memory_order_relaxed);
+  g_dev_records.fetch_add(n, std::memory_order_relaxed);
+  HIPCHK(bh::launch_hash(alg, in, (uint32_t)n, digest, result, s));
+  if (sync) HIPCHK(hipStreamSynchronize(s));
+  return BH_OK;
 }
 
 int bh_pack_stats(double out[10]) {

@@ -326,8 +326,13 @@ bool dec_action_payload(Span in, ActionPayload* o) {
   });
 }
 
-bool dec_prp(Span in) {  // peer.ProposalResponsePayload: bytes fields only
-  return pb_walk(in.p, in.n, [&](const Field&) { return true; });
+// peer.ProposalResponsePayload: bytes fields only; proposal_hash is kept for
+// the proposal-hash check (bh_fabric_block_prevalidate)
+bool dec_prp(Span in, Span* proposal_hash) {
+  return pb_walk(in.p, in.n, [&](const Field& f) {
+    if (is_bytes(f, 1)) *proposal_hash = f.s;
+    return true;
+  });
 }
 
 struct SerializedIdentity {  // msp.SerializedIdentity
@@ -1022,12 +1027,23 @@ struct TxRec {
   size_t end_first = 0, end_count = 0;  // endorsements in the shared entry list
 };
 
+// bh_fabric_block_prevalidate: the inputs of CheckTxID (once the common header
+// validated) and of the proposal hash (once the endorser-transaction structure
+// decoded), as the decode walks past them. Kept beside TxRec, and only for
+// that call: the older calls decode into what they always did.
+struct TxHashIn {
+  Span nonce, creator, txid, chdr, ashdr, ccpp, phash;
+  bool txid_check = false;   // ENDORSER_TRANSACTION whose common header validated
+  bool phash_check = false;  // ... whose endorser-transaction structure decoded
+};
+
 // Go's order of checks up to the signatures (validateTx, ValidateTransaction,
 // validateEndorserTransaction). Checks that do not gate which signatures are
-// verified (CheckTxID, the proposal hash, ledger / channel state) are left to
-// the unchanged validator. Pure parsing (no identity lookups), so transactions
+// verified (ledger / channel state) are left to the unchanged validator;
+// CheckTxID and the proposal hash are checked by bh_fabric_block_prevalidate
+// alone, from the spans kept here. Pure parsing (no identity lookups), so transactions
 // decode in parallel; resolve_tx then applies the identity outcomes.
-void decode_tx(Span env_bytes, TxRec* t, std::vector<SdEntry>* ends) {
+void decode_tx(Span env_bytes, TxRec* t, std::vector<SdEntry>* ends, TxHashIn* hx = nullptr) {
   t->end_first = ends->size();
   Envelope env;
   if (!dec_envelope(env_bytes, &env)) {
@@ -1051,6 +1067,13 @@ void decode_tx(Span env_bytes, TxRec* t, std::vector<SdEntry>* ends) {
     return;
   }
   t->type = ch.type;
+  if (hx) {
+    hx->nonce = sh.nonce;
+    hx->creator = sh.creator;
+    hx->txid = ch.tx_id;
+    hx->chdr = pl.header.channel_header;
+    hx->txid_check = ch.type == 3;  // CheckTxID (msgvalidation.go:288-296)
+  }
   // checkSignatureFromCreator: nil arguments, then DeserializeIdentity (in
   // resolve_tx: BH_FAB_CREATOR_IDENTITY overrides everything below), Verify
   t->payload = env.payload;
@@ -1071,6 +1094,7 @@ void decode_tx(Span env_bytes, TxRec* t, std::vector<SdEntry>* ends) {
   std::vector<TxAction> acts;
   int32_t tx_status = BH_FAB_OK;
   ActionPayload ap;
+  Span phash;
   if (!dec_transaction(pl.data, &acts) || acts.size() != 1) {
     tx_status = BH_FAB_TX;
   } else {
@@ -1078,12 +1102,18 @@ void decode_tx(Span env_bytes, TxRec* t, std::vector<SdEntry>* ends) {
     if (!dec_signature_header(acts[0].header, &ash) || ash.nonce.n == 0 || ash.creator.n == 0 ||
         !dec_action_payload(acts[0].payload, &ap) ||
         !ap.has_action /* Go dereferences a nil Action here */ ||
-        !dec_prp(ap.action.prp))
+        !dec_prp(ap.action.prp, &phash))
       tx_status = BH_FAB_TX;
   }
   if (tx_status != BH_FAB_OK) {
     t->post_status = tx_status;
     return;
+  }
+  if (hx) {
+    hx->ashdr = acts[0].header;
+    hx->ccpp = ap.ccpp;
+    hx->phash = phash;
+    hx->phash_check = true;  // msgvalidation.go:228-241
   }
   for (const Endorsement& en : ap.action.endorsements) {
     // SignedData{data: prp || endorser, identity: endorser, signature}
@@ -1240,7 +1270,7 @@ class Pool {
 // The outcome does not depend on the order identities are resolved in: a
 // memo or the cache only returns what resolve() makes of the same bytes.
 void decode_block_txs(const std::vector<Span>& data, std::vector<TxRec>* t,
-                      std::vector<SdEntry>* ends) {
+                      std::vector<SdEntry>* ends, std::vector<TxHashIn>* hx = nullptr) {
   const size_t n = data.size();
   Pool& pool = Pool::get();
   const size_t chunks = std::min<size_t>(n / 16 + 1, 4 * pool.size());
@@ -1250,7 +1280,8 @@ void decode_block_txs(const std::vector<Span>& data, std::vector<TxRec>* t,
   pool.run(chunks, [&](size_t c) {
     const size_t lo = n * c / chunks, hi = n * (c + 1) / chunks;
     part[c].reserve((hi - lo) * 4);
-    for (size_t i = lo; i < hi; i++) decode_tx(data[i], &(*t)[i], &part[c]);
+    for (size_t i = lo; i < hi; i++)
+      decode_tx(data[i], &(*t)[i], &part[c], hx ? &(*hx)[i] : nullptr);
     IdentMemo memo(ic, &ic_mu);  // end_first is chunk-relative until the merge below
     for (size_t i = lo; i < hi; i++) resolve_tx(&(*t)[i], part[c].data(), memo);
   });
@@ -1536,7 +1567,7 @@ struct Prestage {
 static int block_preverify(const uint8_t* block, size_t len, uint32_t flags, bh_fab_tx* txs,
                            size_t tx_cap, size_t* n_tx, uint8_t* endorse, size_t endorse_cap,
                            size_t* n_endorse, bh_fab_sigref* refs, size_t ref_cap,
-                           size_t* n_ref) {
+                           size_t* n_ref, bh_fab_txhash* hashes = nullptr) {
   if (!n_tx || !n_endorse || (len && !block) || (n_ref && !refs && ref_cap))
     return bh::host_fail(BH_E_INVALID, "null argument");
   if (flags & ~(uint32_t)(BH_FAB_F_SHA3 | BH_FAB_F_KEEP_KEYS | BH_FAB_F_DECODE_ONLY))
@@ -1553,7 +1584,8 @@ static int block_preverify(const uint8_t* block, size_t len, uint32_t flags, bh_
   const auto T1 = std::chrono::steady_clock::now();
   std::vector<TxRec> t(data.size());
   std::vector<SdEntry> ends;
-  decode_block_txs(data, &t, &ends);
+  std::vector<TxHashIn> hx(hashes ? data.size() : 0);
+  decode_block_txs(data, &t, &ends, hashes ? &hx : nullptr);
   const auto T2 = std::chrono::steady_clock::now();
   *n_tx = t.size();
   *n_endorse = ends.size();
@@ -1585,8 +1617,61 @@ static int block_preverify(const uint8_t* block, size_t len, uint32_t flags, bh_
   std::vector<uint32_t> valid;
   pre.wait();  // its H2D is queued: the batch's upload indexes the device copy
   const auto T3 = std::chrono::steady_clock::now();
-  if (int rc = verify_sets(ends, sets, verify_flags(flags), decode_only, &valid, &creators))
-    return rc;
+  // bh_fabric_block_prevalidate: CheckTxID and the proposal hash of every
+  // transaction as one hash job over the block buffer, submitted ahead of the
+  // signatures (its own stream) and collected after them. SHA-256 whatever the
+  // MSPs' hash family: ComputeTxID and GetProposalHash2 are hard-wired to
+  // crypto/sha256.
+  std::vector<uint64_t> h_off, h_woff;
+  std::vector<uint32_t> h_len, h_wlen;
+  std::vector<uint8_t> h_kind, h_res;
+  std::vector<uint32_t> h_txid_rec(hashes ? t.size() : 0, UINT32_MAX),
+      h_phash_rec(hashes ? t.size() : 0, UINT32_MAX);
+  bh_job* hjob = nullptr;
+  if (hashes && !decode_only) {
+    auto off = [&](Span sp) -> uint64_t { return sp.n ? (uint64_t)(sp.p - block) : 0u; };
+    auto rec = [&](Span a, Span b, Span c, Span want, uint8_t kind) {
+      for (const Span& sp : {a, b, c}) {
+        h_off.push_back(off(sp));
+        h_len.push_back((uint32_t)sp.n);
+      }
+      h_woff.push_back(off(want));
+      h_wlen.push_back((uint32_t)want.n);
+      h_kind.push_back(kind);
+      return (uint32_t)(h_kind.size() - 1);
+    };
+    for (size_t i = 0; i < t.size(); i++) {
+      const TxHashIn& x = hx[i];
+      if (x.txid_check)
+        h_txid_rec[i] = rec(x.nonce, x.creator, Span{}, x.txid, BH_HASH_WANT_HEX);
+      // a nil chaincode_proposal_payload (absent, or present with length 0:
+      // protobuf-go stores append([]byte(nil), v...)) is GetProposalHash2's
+      // "nil arguments": nothing to hash
+      if (x.phash_check && x.ccpp.n)
+        h_phash_rec[i] = rec(x.chdr, x.ashdr, x.ccpp, x.phash, BH_HASH_WANT_RAW);
+    }
+    if (!h_kind.empty()) {
+      h_res.assign(h_kind.size(), BH_FAB_H_NOT_CHECKED);
+      bh_hbatch hb{};
+      hb.data = block;
+      hb.data_len = len;
+      hb.off = h_off.data();
+      hb.len = h_len.data();
+      hb.nspan = 3;
+      hb.want_off = h_woff.data();
+      hb.want_len = h_wlen.data();
+      hb.want_kind = h_kind.data();
+      if (int rc = bh_hash_submit(BH_HASH_SHA256, &hb, h_kind.size(), nullptr, h_res.data(), &hjob))
+        return rc;
+    }
+  }
+  {
+    const int rc = verify_sets(ends, sets, verify_flags(flags), decode_only, &valid, &creators);
+    const std::string err = rc ? bh_last_error() : "";
+    const int hrc = hjob ? bh_verify_wait(hjob) : BH_OK;  // collected whatever the signatures did
+    if (rc) return bh::host_fail(rc, err.c_str());
+    if (hrc) return hrc;
+  }
   if (timing) {
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
       return std::chrono::duration<double, std::micro>(b - a).count();
@@ -1601,6 +1686,34 @@ static int block_preverify(const uint8_t* block, size_t len, uint32_t flags, bh_
     if (!decode_only && x.creator_check && x.creator_out != BH_R_OK &&
         (x.status == BH_FAB_OK || x.status == BH_FAB_TX || x.status == BH_FAB_UNSUPPORTED))
       x.status = BH_FAB_CREATOR_SIGNATURE;
+    if (hashes) {
+      bh_fab_txhash& h = hashes[i];
+      memset(&h, 0, sizeof(h));
+      auto put = [&](Span sp, uint64_t* o, uint32_t* n) {
+        *o = sp.n ? (uint64_t)(sp.p - block) : 0u;
+        *n = (uint32_t)sp.n;
+      };
+      const TxHashIn& in = hx[i];
+      put(in.nonce, &h.nonce_off, &h.nonce_len);
+      put(in.creator, &h.creator_off, &h.creator_len);
+      put(in.txid, &h.txid_off, &h.txid_len);
+      put(in.chdr, &h.chdr_off, &h.chdr_len);
+      put(in.ashdr, &h.ashdr_off, &h.ashdr_len);
+      put(in.ccpp, &h.ccpp_off, &h.ccpp_len);
+      put(in.phash, &h.phash_off, &h.phash_len);
+      h.txid = h_txid_rec[i] != UINT32_MAX ? h_res[h_txid_rec[i]] : (uint8_t)BH_FAB_H_NOT_CHECKED;
+      h.proposal_hash =
+          h_phash_rec[i] != UINT32_MAX ? h_res[h_phash_rec[i]] : (uint8_t)BH_FAB_H_NOT_CHECKED;
+      // Go's order once the creator check passed (ValidateTransaction):
+      // CheckTxID, the endorser-transaction structure (a nil chaincode
+      // proposal payload fails GetProposalHash2 there), the proposal hash
+      if (!decode_only && x.type == 3 && (x.status == BH_FAB_OK || x.status == BH_FAB_TX)) {
+        if (in.txid_check && h.txid != BH_HASH_MATCH) x.status = BH_FAB_TXID;
+        else if (x.status == BH_FAB_OK && in.phash_check && !in.ccpp.n) x.status = BH_FAB_TX;
+        else if (x.status == BH_FAB_OK && in.phash_check && h.proposal_hash != BH_HASH_MATCH)
+          x.status = BH_FAB_PROPOSAL_HASH;
+      }
+    }
     txs[i].status = x.status;
     txs[i].type = x.type;
     txs[i].creator = x.creator_out;
@@ -1661,6 +1774,21 @@ extern "C" int bh_fabric_block_preverify_refs(const uint8_t* block, size_t len, 
   if (!n_ref) return bh::host_fail(BH_E_INVALID, "null argument");
   return block_preverify(block, len, flags, txs, tx_cap, n_tx, endorse, endorse_cap, n_endorse,
                          refs, ref_cap, n_ref);
+}
+
+extern "C" int bh_fabric_block_prevalidate(const uint8_t* block, size_t len, uint32_t flags,
+                                           bh_fab_tx* txs, size_t tx_cap, size_t* n_tx,
+                                           uint8_t* endorse, size_t endorse_cap, size_t* n_endorse,
+                                           bh_fab_sigref* refs, size_t ref_cap, size_t* n_ref,
+                                           bh_fab_txhash* hashes) {
+  // hashes: tx_cap entries; like txs it may be NULL only while tx_cap is 0 (a sizing call)
+  if ((!hashes && tx_cap) || (refs && !n_ref)) return bh::host_fail(BH_E_INVALID, "null argument");
+  bh_fab_txhash none;
+  const int rc = block_preverify(block, len, flags, txs, tx_cap, n_tx, endorse, endorse_cap,
+                                 n_endorse, refs, ref_cap, refs ? n_ref : nullptr,
+                                 hashes ? hashes : &none);
+  if (!refs && n_ref && n_tx && n_endorse) *n_ref = *n_tx + *n_endorse;
+  return rc;
 }
 
 // SignatureSetToValidIdentities over many signature sets in one device batch.

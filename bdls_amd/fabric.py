@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 
 FAB_STATUS = {0: "OK", 1: "ENVELOPE", 2: "PAYLOAD", 3: "HEADER", 4: "CREATOR_IDENTITY",
-              5: "CREATOR_SIGNATURE", 6: "TX", 7: "UNSUPPORTED"}
+              5: "CREATOR_SIGNATURE", 6: "TX", 7: "UNSUPPORTED", 8: "TXID", 9: "PROPOSAL_HASH"}
 E_DUPLICATE, E_BAD_IDENTITY, NOT_VERIFIED = 253, 254, 255
 
 
@@ -115,6 +115,68 @@ def block_preverify_refs(block: bytes, sha3: bool = False, keep_keys: bool = Fal
     creators = [ref(refs[i]) for i in range(ntx.value)]
     endorsements = [ref(refs[ntx.value + j]) for j in range(nend.value)]
     return out, creators, endorsements
+
+
+H_MATCH, H_MISMATCH, H_NOT_CHECKED = 0, 1, 0xFF
+
+
+@dataclass
+class TxHash:
+    """bh_fab_txhash: the outcome of CheckTxID and of the proposal-hash check
+    (H_MATCH / H_MISMATCH / H_NOT_CHECKED) and where their inputs lie in the
+    block, as (offset, length); length 0 = the decode never reached it."""
+    txid: int
+    proposal_hash: int
+    spans: dict  # nonce / creator / txid / chdr / ashdr / ccpp / phash -> (off, len)
+
+
+def block_prevalidate(block: bytes, sha3: bool = False, keep_keys: bool = False,
+                      decode_only: bool = False):
+    """block_preverify_refs plus CheckTxID and the proposal hash of every
+    endorser transaction on the device (bh_fabric_block_prevalidate). Returns
+    (transactions, creator SigRefs, endorsement SigRefs, per-transaction
+    TxHash); TxResult.status is the first failing check in Go's order, with
+    BH_FAB_TXID / BH_FAB_PROPOSAL_HASH among them."""
+    L = _lib.lib()
+    if not decode_only:
+        _lib.ensure_init()
+    flags = _flags(sha3, keep_keys, decode_only)
+    buf = np.frombuffer(bytes(block) + b"\0", np.uint8)
+    ntx, nend, nref = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    rc = L.bh_fabric_block_prevalidate(buf.ctypes.data, len(block),
+                                       flags | _lib.BH_FAB_F_DECODE_ONLY, None, 0,
+                                       ctypes.byref(ntx), None, 0, ctypes.byref(nend), None, 0,
+                                       ctypes.byref(nref), None)
+    if rc != 0 and nref.value == 0:
+        _lib.check(rc)
+    txs = (_lib.BhFabTx * max(1, ntx.value))()
+    end = np.zeros(max(1, nend.value), np.uint8)
+    refs = (_lib.BhFabSigref * max(1, nref.value))()
+    hs = (_lib.BhFabTxhash * max(1, ntx.value))()
+    _lib.check(L.bh_fabric_block_prevalidate(
+        buf.ctypes.data, len(block), flags, txs, ntx.value, ctypes.byref(ntx), end.ctypes.data,
+        nend.value, ctypes.byref(nend), refs, nref.value, ctypes.byref(nref), hs))
+    assert nref.value == ntx.value + nend.value
+    out, hashes = [], []
+    for i in range(ntx.value):
+        t, h = txs[i], hs[i]
+        out.append(TxResult(t.status, t.type, t.creator,
+                            [int(x) for x in end[t.endorse_first:t.endorse_first + t.endorse_count]],
+                            t.valid_endorsers))
+        hashes.append(TxHash(int(h.txid), int(h.proposal_hash),
+                             {s: (int(getattr(h, s + "_off")), int(getattr(h, s + "_len")))
+                              for s in _lib.BhFabTxhash.SPANS}))
+
+    def ref(r):
+        if r.ident_len == 0:
+            return None
+        sp = lambda off, n: bytes(block[off:off + n])  # noqa: E731
+        return SigRef(sp(r.ident_off, r.ident_len),
+                      sp(r.msg_off, r.msg_len) + sp(r.msg2_off, r.msg2_len),
+                      sp(r.sig_off, r.sig_len), int(r.reason))
+    creators = [ref(refs[i]) for i in range(ntx.value)]
+    endorsements = [ref(refs[ntx.value + j]) for j in range(nend.value)]
+    return out, creators, endorsements, hashes
 
 
 def _concat(items):

@@ -2,7 +2,7 @@
 
 `kernel_src_sha()` hashes the sources the HIP code object is compiled from
 (the kernel units linked into the library -- bdls_amd/csrc/verify_kernels.hip,
-verify384_kernels.hip, sha512_kernels.hip -- every header under bdls_amd/csrc/,
+verify384_kernels.hip, sha512_kernels.hip, hash_kernels.hip -- every header under bdls_amd/csrc/,
 and the Makefile that holds the compile flags). build() records it in
 bdls_amd/lib/BUILD_INFO.json with the library's sha256, tools/pmc_summary.py
 stamps it into profiles/traffic.json, and bench.py prints PMC counters only
@@ -26,7 +26,7 @@ def kernel_sources() -> list[str]:
     csrc = os.path.join(ROOT, "bdls_amd", "csrc")
     return sorted(glob.glob(os.path.join(csrc, "*.h"))) + \
         [os.path.join(csrc, f) for f in ("verify_kernels.hip", "verify384_kernels.hip",
-                                         "sha512_kernels.hip")] + \
+                                         "sha512_kernels.hip", "hash_kernels.hip")] + \
         [os.path.join(ROOT, "Makefile")]
 
 

@@ -251,9 +251,26 @@ CORRUPTIONS = ["none", "creator_sig_flip", "creator_high_s", "endorse_sig_flip",
                "creator_bad_identity", "two_actions", "endorse_dup_after_invalid",
                "envelope_garbage"]
 
+# Corruptions of the two SHA-256 checks of an endorser transaction (CheckTxID,
+# the proposal hash: bh_fabric_block_prevalidate), reachable only through
+# `classes=` -- not part of CORRUPTIONS, whose length seeds the random choice.
+# In all of them the creator signs the final payload and the endorsers the
+# final prp: every signature stays valid and the transaction fails on the hash
+# alone.
+HASH_CLASSES = ["txid_wrong", "txid_upper", "txid_short", "txid_empty", "phash_wrong",
+                "phash_short", "phash_long", "phash_absent", "ccpp_empty", "ccpp_absent",
+                "txid_and_phash_wrong", "txid_wrong_two_actions"]
+_TXID_BAD = {"txid_wrong", "txid_upper", "txid_short", "txid_empty", "txid_and_phash_wrong",
+             "txid_wrong_two_actions"}
+_PHASH_BAD = {"phash_wrong", "phash_short", "phash_long", "phash_absent", "txid_and_phash_wrong"}
+_TWO_ACTIONS = {"two_actions", "txid_wrong_two_actions"}
+_CCPP_NIL = {"ccpp_empty", "ccpp_absent"}
+
 # expected results (bdls_hip.h BH_FAB_* statuses, BH_R_* reasons)
 FAB_OK, FAB_ENVELOPE, FAB_PAYLOAD, FAB_HEADER, FAB_CREATOR_IDENTITY = 0, 1, 2, 3, 4
 FAB_CREATOR_SIGNATURE, FAB_TX = 5, 6
+FAB_TXID, FAB_PROPOSAL_HASH = 8, 9
+H_MATCH, H_MISMATCH, H_NOT_CHECKED = 0, 1, 0xFF
 E_DUP, E_BAD_IDENTITY, E_NOT_VERIFIED = 253, 254, 255
 
 
@@ -265,6 +282,11 @@ class FabricBlock:
     tx_endorse: list[list[int]] = field(default_factory=list)
     tx_valid_identities: list[int] = field(default_factory=list)
     tx_class: list[str] = field(default_factory=list)
+    # the outcome of bh_fabric_block_prevalidate (the fields above keep
+    # describing bh_fabric_block_preverify): status with BH_FAB_TXID /
+    # BH_FAB_PROPOSAL_HASH in Go's order, and (txid, proposal_hash) checks
+    tx_status_full: list[int] = field(default_factory=list)
+    tx_hash: list[tuple] = field(default_factory=list)
     n_signatures: int = 0
     p384_keys: set = field(default_factory=set)  # (x, y) of every P-384 identity generated
     identities: list = field(default_factory=list)  # peers, then clients
@@ -322,13 +344,31 @@ def generate_fabric_block(ntx: int = 500, endorsements: int = 3, norgs: int = 4,
         nonce = _rand_bytes(st, 24)
         creator_ser = bad_ident if cls == "creator_bad_identity" else creator.serialized
         txid = hashlib.sha256(nonce + creator_ser).hexdigest()
+        if cls in ("txid_wrong", "txid_and_phash_wrong", "txid_wrong_two_actions"):
+            txid = ("1" if txid[0] == "0" else "0") + txid[1:]  # one hex digit
+        elif cls == "txid_upper":
+            txid = txid.upper()
+            assert txid != txid.lower()
+        elif cls == "txid_short":
+            txid = txid[:63]
+        elif cls == "txid_empty":
+            txid = ""
         chdr = (pb_varint(1, 3) + pb_bytes(3, pb_varint(1, 1_750_000_000 + t) + pb_varint(2, t))
                 + pb_bytes(4, b"mychannel") + pb_bytes(5, txid.encode())
                 + (pb_varint(6, 7) if cls == "epoch" else b""))
         shdr = pb_bytes(1, creator_ser) + pb_bytes(2, nonce)
         ccpp = _rand_bytes(st, ccpp_len)
+        if cls in _CCPP_NIL:
+            ccpp = b""  # the hash over the two headers: only the nil payload fails
         phash = hashlib.sha256(chdr + shdr + ccpp).digest()
-        prp = pb_bytes(1, phash) + pb_bytes(2, _rand_bytes(st, ext_len))
+        if cls in ("phash_wrong", "txid_and_phash_wrong"):
+            phash = bytes([phash[0] ^ 0x10]) + phash[1:]  # one bit
+        elif cls == "phash_short":
+            phash = phash[:31]
+        elif cls == "phash_long":
+            phash = phash + b"\x00"
+        prp = ((b"" if cls == "phash_absent" else pb_bytes(1, phash))
+               + pb_bytes(2, _rand_bytes(st, ext_len)))
         eps = [peers[(t + k) % len(peers)] for k in range(min(endorsements, len(peers)))]
         txs.append(dict(cls=cls, creator=creator, chdr=chdr, shdr=shdr, ccpp=ccpp, prp=prp,
                         eps=eps))
@@ -377,9 +417,9 @@ def generate_fabric_block(ntx: int = 500, endorsements: int = 3, norgs: int = 4,
             expect_e = expect_e[:len(tx["eps"])]
         endorsements_pb = b"".join(pb_bytes(2, pb_bytes(1, e) + pb_bytes(2, s)) for e, s in ends)
         cea = pb_bytes(1, tx["prp"]) + endorsements_pb
-        ccap = pb_bytes(1, tx["ccpp"]) + pb_bytes(2, cea)
+        ccap = (b"" if cls == "ccpp_absent" else pb_bytes(1, tx["ccpp"])) + pb_bytes(2, cea)
         action = pb_bytes(1, tx["shdr"]) + pb_bytes(2, ccap)
-        txn = pb_bytes(1, action) + (pb_bytes(1, action) if cls == "two_actions" else b"")
+        txn = pb_bytes(1, action) + (pb_bytes(1, action) if cls in _TWO_ACTIONS else b"")
         payload = pb_bytes(1, pb_bytes(1, tx["chdr"]) + pb_bytes(2, tx["shdr"])) + pb_bytes(2, txn)
         if cls == "payload_garbage":
             payload = b"\x0a\xff\xff\x03" + payload
@@ -415,7 +455,7 @@ def generate_fabric_block(ntx: int = 500, endorsements: int = 3, norgs: int = 4,
             status, creator_r = FAB_CREATOR_SIGNATURE, 9
         elif cls == "creator_high_s":
             status, creator_r = FAB_CREATOR_SIGNATURE, 6
-        elif cls == "two_actions":
+        elif cls in _TWO_ACTIONS:
             status = FAB_TX
         if status in (FAB_ENVELOPE, FAB_PAYLOAD, FAB_HEADER, FAB_TX):
             endorse = []
@@ -425,6 +465,24 @@ def generate_fabric_block(ntx: int = 500, endorsements: int = 3, norgs: int = 4,
         fb.tx_endorse.append(endorse)
         fb.tx_valid_identities.append(valid_ids)
         fb.tx_class.append(cls)
+        # the two hash checks, in Go's order after the creator check: CheckTxID
+        # (every endorser transaction whose common header validated), the
+        # structure (a nil chaincode proposal payload fails there), the
+        # proposal hash (every transaction whose structure decoded)
+        headed = status not in (FAB_ENVELOPE, FAB_PAYLOAD, FAB_HEADER)
+        h_txid = H_NOT_CHECKED if not headed else H_MISMATCH if cls in _TXID_BAD else H_MATCH
+        h_phash = (H_NOT_CHECKED if (not headed or cls in _TWO_ACTIONS or cls in _CCPP_NIL)
+                   else H_MISMATCH if cls in _PHASH_BAD else H_MATCH)
+        full = status
+        if status in (FAB_OK, FAB_TX):
+            if h_txid == H_MISMATCH:
+                full = FAB_TXID
+            elif status == FAB_OK and cls in _CCPP_NIL:
+                full = FAB_TX
+            elif status == FAB_OK and h_phash == H_MISMATCH:
+                full = FAB_PROPOSAL_HASH
+        fb.tx_status_full.append(full)
+        fb.tx_hash.append((h_txid, h_phash))
         fb.n_signatures += (creator_r != E_NOT_VERIFIED) + sum(r <= 10 for r in endorse)
     data = b"".join(pb_bytes(1, e) for e in envs)
     data_hash = hashlib.sha256(b"".join(envs)).digest()

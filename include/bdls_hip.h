@@ -430,6 +430,74 @@ int bh_batch_verify384_ptrs_submit(const bh_pbatch *b, size_t n, uint32_t flags,
  * phase 1 already verified). Not in the reference: an observability hook. */
 int bh_device_stats(uint64_t out[2]);
 
+/* ---- Batched Hash -------------------------------------------------------------
+ * CSP.Hash (bccsp/bccsp.go:109, bccsp/sw/impl.go:177-194) as a batch, and the
+ * two SHA-256 checks of a pre-verified block's endorser transactions:
+ *   - protoutil.CheckTxID (core/common/validation/msgvalidation.go:288-296):
+ *     hex(SHA-256(nonce || creator)) == ChannelHeader.tx_id, as
+ *     protoutil/proputils.go:351-370 computes it (BAD_PROPOSAL_TXID), and
+ *   - the proposal hash (msgvalidation.go:228-241): SHA-256(channel_header ||
+ *     action header || chaincode_proposal_payload) ==
+ *     ProposalResponsePayload.proposal_hash, as protoutil/txutils.go:449-466
+ *     (GetProposalHash2) computes it (INVALID_ENDORSER_TRANSACTION).
+ * Record i is the nspan spans data[off[i*nspan + k], +len[i*nspan + k]), k <
+ * nspan, hashed as one message in that order; a zero-length span contributes
+ * nothing (its offset must still lie inside the buffer). alg is BH_HASH_SHA256
+ * (Go crypto/sha256) or BH_HASH_SHA3_256 (x/crypto sha3.New256). SHA-384,
+ * SHA-512 and SHA3-384 are not offered here: the wide SHA-2 digests exist on
+ * the device only as the digest pass of the curve calls (BH_F_HASH_SHA384 /
+ * BH_F_HASH_SHA512).
+ * Outputs, either or both:
+ *   digest[i]  32 bytes, the standard digest (hashlib's .digest())
+ *   result[i]  the digest compared with the expected span data[want_off[i],
+ *              +want_len[i]) under want_kind[i]:
+ *                BH_HASH_WANT_RAW  equal iff want_len == 32 and the bytes match
+ *                BH_HASH_WANT_HEX  equal iff want_len == 64 and the bytes are
+ *                                  the lowercase hex of the digest (Go's
+ *                                  hex.EncodeToString and a string compare:
+ *                                  upper case does not match)
+ *              any other kind is BH_HASH_MISMATCH.
+ *   BH_HASH_RANGE (a span or the expected span ends beyond data_len): the
+ *   record reads nothing and its digest is zeros.
+ * bh_hash / bh_hash_submit take host memory. They check, before any device
+ * work and with BH_E_INVALID and a bh_last_error text: alg; nspan in 1..3;
+ * NULL b / data / off / len; digest and result both NULL; want_* partly NULL;
+ * result without want_*; every span and expected span inside data_len (no sum
+ * that can wrap), n <= 2^32 - 1. These checks need no device; BH_E_NOT_INIT
+ * comes after them. n == 0 is BH_OK (a submit form still returns a job).
+ * The batch runs on the first initialised device (no sharding), on a stream
+ * of its own, not behind the compute lanes: a hash job submitted before a
+ * verify call overlaps it. When `data` is the buffer the calling thread has
+ * pre-staged (the block of bh_fabric_block_prevalidate), the records index
+ * its device mirror and the data is not uploaded again; otherwise the call
+ * uploads the bytes the records cover. bh_hash_submit's job is collected with
+ * bh_verify_wait (exactly once, in any order among other jobs), which writes
+ * digest / result; the caller's buffers stay valid and unchanged until then.
+ * bh_device_stats counts a hash job as one batch and its n records.
+ * bh_hash_dev: b is a host struct of DEVICE pointers on `device`, digest /
+ * result device memory; stream NULL = the device's hash stream; sync != 0
+ * waits. It cannot see the arrays, so the kernel's BH_HASH_RANGE is its guard
+ * (data must lie in a device allocation: whole aligned dwords are loaded). */
+#define BH_HASH_SHA256   1
+#define BH_HASH_SHA3_256 2
+#define BH_HASH_WANT_RAW 0
+#define BH_HASH_WANT_HEX 1
+#define BH_HASH_MATCH    0
+#define BH_HASH_MISMATCH 1
+#define BH_HASH_RANGE    2
+typedef struct bh_hbatch {
+  const uint8_t  *data;  size_t data_len;     /* every span indexes this buffer */
+  const uint64_t *off;   const uint32_t *len; /* n * nspan, record-major */
+  uint32_t nspan;                             /* 1..3 */
+  const uint64_t *want_off; const uint32_t *want_len; const uint8_t *want_kind; /* or all NULL */
+} bh_hbatch;
+int bh_hash(int alg, const bh_hbatch *b, size_t n, uint8_t *digest /* n*32 or NULL */,
+            uint8_t *result /* n or NULL */);
+int bh_hash_submit(int alg, const bh_hbatch *b, size_t n, uint8_t *digest, uint8_t *result,
+                   bh_job **job);             /* collected with bh_verify_wait */
+int bh_hash_dev(int device, int alg, const bh_hbatch *b /* device pointers */, size_t n,
+                uint8_t *digest, uint8_t *result, void *stream, int sync);
+
 /* Host-side Go-exact DER unmarshal (bccsp/utils/ecdsa.go:41-65). Returns the
  * reason (BH_R_OK, BH_R_DER, BH_R_R_NONPOS, BH_R_S_NONPOS); on BH_R_OK fills
  * r, s (32-byte big-endian) or sets *r_big / *s_big when a value exceeds 256
@@ -583,7 +651,8 @@ int bh_bdls_preverify(int curve, const uint8_t *msgs, const uint64_t *msg_off,
  * made. The same holds for the signature-set, envelope and block-signature
  * entry points below. Checks that do not decide which signatures are verified
  * (CheckTxID, the proposal hash, channel / ledger state, policies) stay with
- * the unchanged validator, which consults the per-signature results.
+ * the unchanged validator, which consults the per-signature results
+ * (bh_fabric_block_prevalidate below adds CheckTxID and the proposal hash).
  *
  * txs[i] (tx_cap >= number of transactions) and endorse[] (one byte per
  * endorsement, tx i's at [endorse_first, +endorse_count)); *n_tx and
@@ -645,6 +714,58 @@ int bh_fabric_block_preverify_refs(const uint8_t *block, size_t len, uint32_t fl
                                    bh_fab_tx *txs, size_t tx_cap, size_t *n_tx, uint8_t *endorse,
                                    size_t endorse_cap, size_t *n_endorse, bh_fab_sigref *refs,
                                    size_t ref_cap, size_t *n_ref);
+
+/* bh_fabric_block_preverify_refs plus the two SHA-256 checks that
+ * ValidateTransaction makes of an endorser transaction once its creator
+ * signature verified, on the device (one bh_hash job over the block buffer,
+ * submitted ahead of the signature batch on its own stream and collected
+ * after it):
+ *   - protoutil.CheckTxID (core/common/validation/msgvalidation.go:288-296):
+ *     hex(SHA-256(nonce || creator)) == ChannelHeader.tx_id
+ *     (protoutil/proputils.go:351-370), else BAD_PROPOSAL_TXID;
+ *   - the proposal hash (msgvalidation.go:228-241): SHA-256(channel_header ||
+ *     actions[0].header || chaincode_proposal_payload) ==
+ *     ProposalResponsePayload.proposal_hash (GetProposalHash2,
+ *     protoutil/txutils.go:449-466), else INVALID_ENDORSER_TRANSACTION.
+ * Both are SHA-256 whatever the flags: ComputeTxID and GetProposalHash2 are
+ * hard-wired to crypto/sha256, and BH_FAB_F_SHA3 changes only the signatures'
+ * family. With them no host cryptography is left in ValidateTransaction for a
+ * pre-validated block.
+ * hashes[i] (tx_cap entries): txid is checked for every ENDORSER_TRANSACTION
+ * whose common header validated; proposal_hash for those whose endorser-
+ * transaction structure decoded, except that a chaincode_proposal_payload that
+ * is absent or present with length 0 is nil in Go (protobuf-go's proto3 bytes
+ * decoder stores append([]byte(nil), v...)): GetProposalHash2 answers "nil
+ * arguments", so that transaction is BH_FAB_TX with proposal_hash =
+ * BH_FAB_H_NOT_CHECKED. CONFIG / CONFIG_UPDATE transactions and anything that
+ * failed earlier in the decode get BH_FAB_H_NOT_CHECKED for both. The spans
+ * nonce / creator / txid / chdr are filled once the common header validated
+ * (any type), ashdr / ccpp / phash once the endorser-transaction structure
+ * decoded; len 0 = the decode never reached it (or the field is empty).
+ * txs[i].status is the first failing check in Go's order: ENVELOPE / PAYLOAD /
+ * HEADER / CREATOR_IDENTITY / CREATOR_SIGNATURE / UNSUPPORTED as before, then
+ * BH_FAB_TXID, BH_FAB_TX, BH_FAB_PROPOSAL_HASH. txs[i].type / creator /
+ * endorse_* / valid_endorsers, endorse[] and refs[] are exactly what
+ * bh_fabric_block_preverify_refs gives for the same block and flags. refs may
+ * be NULL (*n_ref is still set when n_ref is given). With
+ * BH_FAB_F_DECODE_ONLY the spans are filled, both checks are
+ * BH_FAB_H_NOT_CHECKED and the statuses are the old call's. A consumer keys
+ * hashes[i] like the signature cache and falls back to the Go checks on
+ * BH_FAB_H_NOT_CHECKED. */
+#define BH_FAB_TXID 8            /* CheckTxID failed: BAD_PROPOSAL_TXID (msgvalidation.go:288-296) */
+#define BH_FAB_PROPOSAL_HASH 9   /* proposal hash differs: INVALID_ENDORSER_TRANSACTION (:228-241) */
+#define BH_FAB_H_NOT_CHECKED 0xff
+typedef struct bh_fab_txhash {
+  uint8_t txid, proposal_hash;   /* BH_HASH_MATCH / BH_HASH_MISMATCH / BH_FAB_H_NOT_CHECKED */
+  uint8_t reserved[6];
+  /* where the inputs lie in `block` (len 0 = the decode never reached it) */
+  uint64_t nonce_off, creator_off, txid_off, chdr_off, ashdr_off, ccpp_off, phash_off;
+  uint32_t nonce_len, creator_len, txid_len, chdr_len, ashdr_len, ccpp_len, phash_len, pad;
+} bh_fab_txhash;
+int bh_fabric_block_prevalidate(const uint8_t *block, size_t len, uint32_t flags,
+    bh_fab_tx *txs, size_t tx_cap, size_t *n_tx, uint8_t *endorse, size_t endorse_cap,
+    size_t *n_endorse, bh_fab_sigref *refs, size_t ref_cap, size_t *n_ref, /* refs may be NULL */
+    bh_fab_txhash *hashes /* tx_cap entries */);
 
 /* ---- signature sets: SignatureSetToValidIdentities as a batch ------------------
  * common/policies/policy.go:363-395, the batch point of every policy
