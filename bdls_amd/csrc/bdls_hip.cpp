@@ -31,6 +31,7 @@
 #include "comb384.h"
 #include "keys384.h"
 #include "verify384.h"
+#include "pass384.h"
 #include "pack.h"
 #include "shard.h"
 #include "hashspan.h"
@@ -53,23 +54,12 @@ hipError_t launch_gtab384_build(uint32_t* gtab, hipStream_t s);
 hipError_t launch_sha512(int out_bytes, const uint8_t* msg, const uint64_t* msg_off,
                          const uint32_t* msg_len, uint32_t n, uint8_t* dig, uint64_t* off,
                          uint32_t* len, hipStream_t s);
-hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg384& g,
-                                 const Plan384& pl, const uint32_t* gtab, uint32_t n,
-                                 uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipStream_t aux,
-                                 hipEvent_t fork, hipEvent_t join, hipEvent_t* ev);
 hipError_t launch_keys384_register(const KeyReg384& g, const uint8_t* pub, uint32_t n,
                                    uint8_t* status, uint32_t* fresh, uint32_t* bases,
                                    hipStream_t s);
 hipError_t launch_keys384_prep(const uint8_t* pub, const Keys384& kt, const KeyReg384& g,
                                hipStream_t s);
 hipError_t launch_comb384_g(uint32_t* bases, uint32_t* side, uint32_t* gcomb, hipStream_t s);
-hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg384& g,
-                                 bool with_reg, const Comb384& cb, void* zero, size_t zero_bytes,
-                                 const Plan384& pl, const uint32_t* gtab, const uint32_t* gcomb,
-                                 uint32_t n, uint64_t* bitmap, uint8_t* reason, hipStream_t s,
-                                 hipStream_t aux, hipEvent_t fork, hipEvent_t join, hipEvent_t* ev);
-hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* gtab, uint32_t n,
-                            uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev);
 size_t expand_temp_bytes(uint32_t m);
 hipError_t launch_result_out(const void* src, void* host_dst, size_t bytes, hipStream_t s);
 hipError_t launch_hash(int alg, const HashIn& in, uint32_t n, uint8_t* digest, uint8_t* result,
@@ -195,62 +185,54 @@ struct HostBuf {
   }
 };
 
+// What every pipeline slot of a device has (take_slot, finish_part): the events
+// that order upload -> passes -> results and the job that holds the slot.
+struct SlotBase {
+  hipEvent_t uploaded = nullptr, done = nullptr;
+  bh_job* owner = nullptr;  // job whose results are in flight / sit in the page-locked output
+  size_t owner_part = 0;
+};
+
 // One of the host-API pipeline slots of a device (four-deep): its own
 // device staging for the inputs, device and pinned-host buffers for the
 // outputs, and the events that order upload -> verify -> download. While the
 // compute stream verifies one slot's batch, the copy stream uploads the next.
-struct Slot {
+struct Slot : SlotBase {
   HostBuf host_in;  // latency path: the small batch packed on the host
   DevBuf stage;     // inputs (H2D on the copy stream)
   DevBuf out;       // bitmap words + reasons (device)
   // bitmap words + reasons (pinned, coherent: written by the compute stream's
   // k_result_out, read by the host after the slot's done event)
   HostBuf host_out{nullptr, 0, hipHostMallocPortable | hipHostMallocCoherent};
-  hipEvent_t uploaded = nullptr, done = nullptr;
   hipEvent_t keys_up = nullptr;  // the key half of the shard uploaded
   // staged host batches (bh_batch_verify*): the shard packed by pack.h into
   // library-owned page-locked memory, reused batch after batch -- keys, key
   // indices and lengths; signature and message bytes
   HostBuf pk_small, pk_bytes;
   HostBuf co_in;  // Uploader's gathered small arrays (batches up to kCoalesceMax bytes)
-  bh_job* owner = nullptr;  // job whose results are in flight / sit in host_out
-  size_t owner_part = 0;
 };
 // up to 4 host batches in flight per device: batch k + 4's upload is queued when
 // batch k is collected, so the copy engine has three uploads of runway while a
 // pass computes (3 slots left it idle ~0.3 ms per batch at config 2)
 constexpr int kSlots = 4;
 
-// One of a device's two P-384 pipeline slots (bh_verify384_compact,
-// bh_batch_verify384_ptrs): a whole shard at a time. Page-locked staging the
-// shard is packed into, its device copy with the shard's key workspace behind
-// it, the shard's bitmap words and reasons on the device and in page-locked
-// memory, and the events upload -> passes -> results. While the P-384 stream
-// runs one slot's chunks, the copy stream uploads the other slot's shard.
-struct Slot384 {
+// A slot of a device's P-384 ring or of its bh_hash ring: page-locked staging
+// the inputs are packed into, their device copy, the results on the device and
+// in page-locked memory.
+// P-384 (bh_verify384_compact, bh_batch_verify384_ptrs): a whole shard at a
+// time, the shard's key workspace behind its device copy, bitmap words and
+// reasons out. While the P-384 stream runs one slot's chunks, the copy stream
+// uploads the other slot's shard.
+// bh_hash: the batch's arrays, the uploaded data bytes behind their device
+// copy, digests and results out. Everything runs on the device's hash stream,
+// so `uploaded` is unused.
+struct StageSlot : SlotBase {
   HostBuf hin;
   DevBuf din;
   DevBuf dout;
   HostBuf hout{nullptr, 0, hipHostMallocPortable | hipHostMallocCoherent};
-  hipEvent_t uploaded = nullptr, done = nullptr;
-  bh_job* owner = nullptr;  // job whose results are in flight / sit in hout
-  size_t owner_part = 0;
 };
 constexpr int kSlots384 = 2;
-
-// One of a device's two bh_hash slots: the batch's arrays packed into
-// page-locked staging, their device copy with the uploaded data bytes behind
-// them, digests and results on the device and in page-locked memory, and the
-// event that ends the job. Everything runs on the device's hash stream.
-struct HashSlot {
-  HostBuf hin;
-  DevBuf din;
-  DevBuf dout;
-  HostBuf hout{nullptr, 0, hipHostMallocPortable | hipHostMallocCoherent};
-  hipEvent_t done = nullptr;
-  bh_job* owner = nullptr;  // job whose results are in flight / sit in hout
-  size_t owner_part = 0;
-};
 constexpr int kHashSlots = 2;
 
 // The extra compute lanes of a device (round 3: one; round 4: up to
@@ -288,14 +270,14 @@ struct Dev {
   bh::KeyReg384 reg384{};    // cap == 0: not allocated
   size_t reg384_count = 0;   // keys registered (the device's count, read back by register)
   DevBuf kb384;              // bh_keys384_register: keys, status, fresh slots, window bases
-  Slot384 s384[kSlots384];   // bh_verify384_compact / bh_batch_verify384_ptrs
+  StageSlot s384[kSlots384];  // bh_verify384_compact / bh_batch_verify384_ptrs
   uint32_t next_s384 = 0;
   // BH_F_HASH_SHA384 / BH_F_HASH_SHA512 (allocated at the device's first such call, under mu)
   DevBuf dig512;  // one chunk's digests, offsets and lengths: the curve pass's digest batch
   hipEvent_t ev512[2] = {nullptr, nullptr};
   // bh_hash (made at the device's first hash call, under mu)
   hipStream_t hstream = nullptr;  // hash jobs: beside the compute lanes, not behind them
-  HashSlot hslot[kHashSlots];
+  StageSlot hslot[kHashSlots];
   uint32_t next_hslot = 0;
   DevBuf ws;     // Work + Plan
   DevBuf stage;  // key registration input
@@ -548,7 +530,7 @@ int dev_init(Dev& d, int id) {
                                                  (blocking_sync() ? hipEventBlockingSync : 0u)));
     HIPCHK(hipEventCreateWithFlags(&sl.keys_up, hipEventDisableTiming));
   }
-  for (Slot384& sl : d.s384) {
+  for (StageSlot& sl : d.s384) {
     HIPCHK(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming |
                                                  (blocking_sync() ? hipEventBlockingSync : 0u)));
@@ -614,7 +596,8 @@ void dev_free(Dev& d) {
   d.reg384_count = 0;
   g_reg384_gen.fetch_add(1, std::memory_order_relaxed);
   d.kb384.release();
-  for (Slot384& sl : d.s384) {
+  if (d.hstream) (void)hipStreamSynchronize(d.hstream);
+  auto free_slot = [](StageSlot& sl) {
     sl.hin.release();
     sl.din.release();
     sl.dout.release();
@@ -622,16 +605,9 @@ void dev_free(Dev& d) {
     if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
     if (sl.done) (void)hipEventDestroy(sl.done);
     sl.uploaded = sl.done = nullptr;
-  }
-  if (d.hstream) (void)hipStreamSynchronize(d.hstream);
-  for (HashSlot& sl : d.hslot) {
-    sl.hin.release();
-    sl.din.release();
-    sl.dout.release();
-    sl.hout.release();
-    if (sl.done) (void)hipEventDestroy(sl.done);
-    sl.done = nullptr;
-  }
+  };
+  for (StageSlot& sl : d.s384) free_slot(sl);
+  for (StageSlot& sl : d.hslot) free_slot(sl);
   if (d.hstream) (void)hipStreamDestroy(d.hstream);
   d.hstream = nullptr;
   d.dig512.release();
@@ -1248,14 +1224,18 @@ const T* dev_batch(const T& d) {
   return &d;
 }
 
+enum class PartKind {
+  batch,  // slot indexes Dev::slot: bitmap words and reasons
+  small,  // latency path, Dev::slot: reasons only (bitmap formed here)
+  p384,   // slot indexes Dev::s384 (a P-384 shard)
+  hash,   // slot indexes Dev::hslot (a bh_hash job)
+};
 struct Part {
   Dev* d;
   int slot;
   size_t lo, m;
   bool done;
-  bool small = false;  // latency path: reasons only (bitmap formed here)
-  bool p384 = false;   // slot indexes Dev::s384 (a P-384 shard), not Dev::slot
-  bool hash = false;   // slot indexes Dev::hslot (a bh_hash job)
+  PartKind kind;
 };
 
 }  // namespace
@@ -1274,54 +1254,54 @@ struct bh_job {
 
 namespace {
 
+// The slot that holds a part's results.
+SlotBase& part_slot(const Part& p) {
+  switch (p.kind) {
+    case PartKind::p384: return p.d->s384[p.slot];
+    case PartKind::hash: return p.d->hslot[p.slot];
+    default: return p.d->slot[p.slot];
+  }
+}
+
 // Wait for part k of job j and copy its results out (caller holds d.mu).
 int finish_part(bh_job* j, size_t k) {
   Part& p = j->parts[k];
   if (p.done) return BH_OK;
   Dev& d = *p.d;
-  if (p.hash) {
-    HashSlot& hs = d.hslot[p.slot];
-    p.done = true;
-    hs.owner = nullptr;
-    HIPCHK(hipSetDevice(d.id));
-    hipError_t eh = hipEventSynchronize(hs.done);
-    if (eh != hipSuccess)
-      return fail(BH_E_DEVICE, std::string("hash pass failed: ") + hipGetErrorString(eh));
-    const uint8_t* o = (const uint8_t*)hs.hout.p;
-    if (j->digest) std::memcpy(j->digest, o, p.m * 32);
-    if (j->hresult) std::memcpy(j->hresult, o + round256(p.m * 32), p.m);
-    return BH_OK;
-  }
-  if (p.p384) {
-    Slot384& s3 = d.s384[p.slot];
-    p.done = true;
-    s3.owner = nullptr;
-    HIPCHK(hipSetDevice(d.id));
-    hipError_t e3 = hipEventSynchronize(s3.done);
-    if (e3 != hipSuccess)
-      return fail(BH_E_DEVICE, std::string("pass failed: ") + hipGetErrorString(e3));
-    const uint64_t* w3 = (const uint64_t*)s3.hout.p;
-    bh::shard_bitmap_merge(j->bitmap, bh::Shard{p.lo, p.m}, w3);  // lo: a multiple of 64
-    std::memcpy(j->reason + p.lo, (const uint8_t*)(w3 + round64(p.m) / 64), p.m);
-    return BH_OK;
-  }
-  Slot& sl = d.slot[p.slot];
+  SlotBase& sl = part_slot(p);
   p.done = true;
   sl.owner = nullptr;
   HIPCHK(hipSetDevice(d.id));
   hipError_t e = hipEventSynchronize(sl.done);
-  if (e != hipSuccess) return fail(BH_E_DEVICE, std::string("pass failed: ") + hipGetErrorString(e));
-  if (p.small) {
-    const uint8_t* rs = (const uint8_t*)sl.host_out.p;
-    std::memcpy(j->reason + p.lo, rs, p.m);
-    for (size_t i = 0; i < p.m; i++)
-      if (rs[i] == BH_R_OK) j->bitmap[(p.lo + i) >> 3] |= (uint8_t)(1u << ((p.lo + i) & 7));
-    return BH_OK;
+  if (e != hipSuccess)
+    return fail(BH_E_DEVICE, std::string(p.kind == PartKind::hash ? "hash pass failed: "
+                                                                   : "pass failed: ") +
+                                 hipGetErrorString(e));
+  switch (p.kind) {
+    case PartKind::hash: {
+      const uint8_t* o = (const uint8_t*)d.hslot[p.slot].hout.p;
+      if (j->digest) std::memcpy(j->digest, o, p.m * 32);
+      if (j->hresult) std::memcpy(j->hresult, o + round256(p.m * 32), p.m);
+      break;
+    }
+    case PartKind::small: {
+      const uint8_t* rs = (const uint8_t*)d.slot[p.slot].host_out.p;
+      std::memcpy(j->reason + p.lo, rs, p.m);
+      for (size_t i = 0; i < p.m; i++)
+        if (rs[i] == BH_R_OK) j->bitmap[(p.lo + i) >> 3] |= (uint8_t)(1u << ((p.lo + i) & 7));
+      break;
+    }
+    case PartKind::p384:
+    case PartKind::batch: {
+      const uint64_t* words = (const uint64_t*)(p.kind == PartKind::p384
+                                                    ? d.s384[p.slot].hout.p
+                                                    : d.slot[p.slot].host_out.p);
+      const uint8_t* rs = (const uint8_t*)(words + round64(p.m) / 64);
+      bh::shard_bitmap_merge(j->bitmap, bh::Shard{p.lo, p.m}, words);  // lo: a multiple of 64
+      std::memcpy(j->reason + p.lo, rs, p.m);
+      break;
+    }
   }
-  const uint64_t* words = (const uint64_t*)sl.host_out.p;
-  const uint8_t* rs = (const uint8_t*)(words + round64(p.m) / 64);
-  bh::shard_bitmap_merge(j->bitmap, bh::Shard{p.lo, p.m}, words);  // lo: a multiple of 64
-  std::memcpy(j->reason + p.lo, rs, p.m);
   return BH_OK;
 }
 
@@ -1349,20 +1329,32 @@ bool keys_first() {
   return on;
 }
 
-// Take the device's next pipeline slot, collecting the batch that still
-// holds it (caller holds d.mu).
-Slot& take_slot(Dev& d, int* k) {
-  *k = (int)(d.next_slot++ % kSlots);
-  Slot& sl = d.slot[*k];
-  if (sl.owner) {  // the slot still holds an uncollected batch: collect it now
-    bh_job* o = sl.owner;
-    int rc = finish_part(o, sl.owner_part);
-    if (rc && o->rc == BH_OK) {
-      o->rc = rc;
-      o->err = g_err;
-    }
+// The job that still holds a slot is collected now; its first error stays with
+// it for its own wait_job (caller holds d.mu).
+void collect_owner(SlotBase& sl) {
+  bh_job* o = sl.owner;
+  if (!o) return;
+  int rc = finish_part(o, sl.owner_part);
+  if (rc && o->rc == BH_OK) {
+    o->rc = rc;
+    o->err = g_err;
   }
-  return sl;
+}
+
+// Take the next slot of one of a device's rings (Dev::slot, s384, hslot with
+// its counter), collecting whoever still holds it (caller holds d.mu).
+template <class S, size_t N>
+S& take_slot(S (&ring)[N], uint32_t& next, int* k) {
+  *k = (int)(next++ % N);
+  collect_owner(ring[*k]);
+  return ring[*k];
+}
+
+// The end of an enqueue: the slot's results belong to the job's next part.
+void bind_owner(SlotBase& sl, bh_job* j, const Part& part) {
+  sl.owner = j;
+  sl.owner_part = j->parts.size();
+  j->parts.push_back(part);
 }
 
 // After a shard's upload is queued on the copy stream (sl.uploaded recorded;
@@ -1394,9 +1386,7 @@ int launch_part(bh_job* j, Dev& d, int k, Slot& sl, int curve, const D& db, size
     HIPCHK(bh::launch_result_out(dbm, sl.host_out.p, round64(m) / 8 + m, s));
   }
   HIPCHK(hipEventRecord(sl.done, s));
-  sl.owner = j;
-  sl.owner_part = j->parts.size();
-  j->parts.push_back(Part{&d, k, lo, m, false});
+  bind_owner(sl, j, Part{&d, k, lo, m, false, PartKind::batch});
   return BH_OK;
 }
 
@@ -1417,7 +1407,7 @@ template <class B>
 int enqueue_part(bh_job* j, Dev& d, int curve, const B* b, size_t lo, size_t m, uint32_t flags) {
   HIPCHK(hipSetDevice(d.id));
   int k;
-  Slot& sl = take_slot(d, &k);
+  Slot& sl = take_slot(d.slot, d.next_slot, &k);
   const HostFields f = fields(b, lo, m);
   int rc;
   if ((rc = sl.stage.ensure(f.bytes + 4096))) return rc;
@@ -1456,10 +1446,13 @@ struct SrcPlain {
   const uint8_t* msg(size_t i) const { return b->msg + b->msg_off[i]; }
   uint32_t msg_len(size_t i) const { return b->msg_len[i]; }
 };
-const uint8_t kZeroKey[64] = {0};
+template <size_t KeyBytes>  // 64, or 96 for P-384
 struct SrcPtrs {
   const bh_pbatch* b;
-  const uint8_t* key(size_t i) const { return b->pub[i] ? b->pub[i] : kZeroKey; }
+  const uint8_t* key(size_t i) const {
+    static const uint8_t zero[KeyBytes] = {0};
+    return b->pub[i] ? b->pub[i] : zero;
+  }
   const uint8_t* sig(size_t i) const { return b->sig[i]; }
   uint32_t sig_len(size_t i) const { return b->sig[i] ? b->sig_len[i] : 0u; }
   const uint8_t* msg(size_t i) const { return b->msg[i]; }
@@ -1552,7 +1545,7 @@ int enqueue_staged(bh_job* j, Dev& d, int curve, const Src& src, size_t lo, size
                    uint32_t flags) {
   HIPCHK(hipSetDevice(d.id));
   int k;
-  Slot& sl = take_slot(d, &k);
+  Slot& sl = take_slot(d.slot, d.next_slot, &k);
   int rc;
   const size_t o_idx = round256(m * 64), o_slen = o_idx + round256(m * 4),
                o_mlen = o_slen + round256(m * 4), small_bytes = o_mlen + round256(m * 4);
@@ -1636,16 +1629,8 @@ template <class Src>
 int enqueue_small(bh_job* j, Dev& d, int curve, const Src& b, size_t lo, size_t m,
                   uint32_t flags) {
   HIPCHK(hipSetDevice(d.id));
-  const int k = (int)(d.next_slot++ % kSlots);
-  Slot& sl = d.slot[k];
-  if (sl.owner) {
-    bh_job* o = sl.owner;
-    int rc = finish_part(o, sl.owner_part);
-    if (rc && o->rc == BH_OK) {
-      o->rc = rc;
-      o->err = g_err;
-    }
-  }
+  int k;
+  Slot& sl = take_slot(d.slot, d.next_slot, &k);
   // layout: pub | sig_off | sig_len | msg_off | msg_len | sig bytes | msg bytes
   size_t sig_bytes = 0, msg_bytes = 0;
   for (size_t i = lo; i < lo + m; i++) {
@@ -1723,11 +1708,7 @@ int enqueue_small(bh_job* j, Dev& d, int curve, const Src& b, size_t lo, size_t 
   HIPCHK(hipEventRecord(sl.done, s));
   HIPCHK(hipEventRecord(L.done, s));
   *L.done_recorded = true;
-  sl.owner = j;
-  sl.owner_part = j->parts.size();
-  Part part{&d, k, lo, m, false};
-  part.small = true;
-  j->parts.push_back(part);
+  bind_owner(sl, j, Part{&d, k, lo, m, false, PartKind::small});
   return BH_OK;
 }
 
@@ -1744,9 +1725,7 @@ int wait_job(bh_job* j) {
     {
       std::lock_guard<std::mutex> g(d.mu);
       const Part& pk = j->parts[k];
-      if (!pk.done)
-        ev = pk.hash ? d.hslot[pk.slot].done
-                     : pk.p384 ? d.s384[pk.slot].done : d.slot[pk.slot].done;
+      if (!pk.done) ev = part_slot(pk).done;
     }
     if (ev) {
       // no early return: every part is still collected (finish_part releases
@@ -1770,45 +1749,35 @@ int wait_job(bh_job* j) {
   return BH_OK;
 }
 
-// Host batch over all initialised devices: contiguous 64-aligned shards,
-// enqueued from the calling thread (every step is asynchronous).
-template <class B>
-int submit_job(int curve, const B* b, size_t n, uint32_t flags, uint8_t* bitmap,
-               uint8_t* reason, bh_job** out) {
-  *out = nullptr;
-  std::vector<Dev*> devs = all_devs();
-  if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
+// A job over n records with nothing enqueued yet; the caller's bitmap cleared.
+bh_job* new_job(uint8_t* bitmap, uint8_t* reason, size_t n) {
   bh_job* j = new bh_job();
   j->bitmap = bitmap;
   j->reason = reason;
   j->n = n;
-  if (n) std::memset(bitmap, 0, (n + 7) / 8);
-  if (small_ok(curve, b, n, flags) && !getenv("BH_NO_SMALL")) {
-    // one device (round robin): a small batch does not shard
-    static std::atomic<uint32_t> rr{0};
-    Dev& d = *devs[rr++ % devs.size()];
-    int rc;
-    {
-      std::lock_guard<std::mutex> g(d.mu);
-      rc = enqueue_small(j, d, curve, SrcPlain{reinterpret_cast<const bh_batch*>(b)}, 0, n,
-                         flags);
-    }
-    if (rc) {
-      const std::string err = g_err;
-      (void)wait_job(j);
-      return fail(rc, err);
-    }
-    *out = j;
-    return BH_OK;
-  }
-  // BH_HOST_SHARDS (default 1): shards per device, dealt round-robin -- the
-  // multi-device shard path (per-shard staging, compact key gather, bitmap
-  // merge at 64-record boundaries) on one device, and a finer upload/compute
-  // pipeline for very large host batches. Up to 8: an 8-GPU node's split on
-  // one device (shards beyond the device's kSlots slots reuse a slot once its
-  // earlier shard -- of this or another job -- is collected, take_slot)
-  size_t per = 1;
-  if (const char* e = getenv("BH_HOST_SHARDS")) per = (size_t)std::max(1, std::min(atoi(e), 8));
+  if (n && bitmap) std::memset(bitmap, 0, (n + 7) / 8);
+  return j;
+}
+
+// BH_HOST_SHARDS (default 1): shards per device, dealt round-robin -- the
+// multi-device shard path (per-shard staging, compact key gather, bitmap
+// merge at 64-record boundaries) on one device, and a finer upload/compute
+// pipeline for very large host batches. Up to 8: an 8-GPU node's split on
+// one device (shards beyond a ring's slots reuse a slot once its earlier
+// shard -- of this or another job -- is collected, take_slot). The P-256 paths
+// read it per call (tests switch it), the P-384 path once per process.
+size_t host_shards() {
+  const char* e = getenv("BH_HOST_SHARDS");
+  return e ? (size_t)std::max(1, std::min(atoi(e), 8)) : size_t(1);
+}
+
+// Deal j's n records over devs, per shards each: contiguous 64-aligned shards
+// (shard.h), enqueued from the calling thread (every step is asynchronous) by
+// enq(j, d, lo, len) under d.mu. One device and per == 1: the batch whole.
+// A failure drains what was enqueued and frees the job; otherwise *out = j.
+template <class Enq>
+int deal_shards(bh_job* j, const std::vector<Dev*>& devs, size_t n, size_t per, bh_job** out,
+                Enq enq) {
   const size_t nd = bh::shard_devices(n, devs.size() * per);
   for (size_t k = 0; k < nd; k++) {
     const bh::Shard sh = bh::shard_of(n, nd, k);
@@ -1817,16 +1786,40 @@ int submit_job(int curve, const B* b, size_t n, uint32_t flags, uint8_t* bitmap,
     int rc;
     {
       std::lock_guard<std::mutex> g(d.mu);
-      rc = enqueue_part(j, d, curve, b, sh.lo, sh.len, flags);
+      rc = enq(j, d, sh.lo, sh.len);
     }
     if (rc) {
       const std::string err = g_err;
-      (void)wait_job(j);  // drain what was enqueued
+      (void)wait_job(j);
       return fail(rc, err);
     }
   }
   *out = j;
   return BH_OK;
+}
+
+// The device of a batch that does not shard: round robin over the initialised ones.
+std::vector<Dev*> next_dev(const std::vector<Dev*>& devs) {
+  static std::atomic<uint32_t> rr{0};
+  return {devs[rr++ % devs.size()]};
+}
+
+// Host batch over all initialised devices; a small one takes the latency path.
+template <class B>
+int submit_job(int curve, const B* b, size_t n, uint32_t flags, uint8_t* bitmap,
+               uint8_t* reason, bh_job** out) {
+  *out = nullptr;
+  std::vector<Dev*> devs = all_devs();
+  if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
+  bh_job* j = new_job(bitmap, reason, n);
+  if (small_ok(curve, b, n, flags) && !getenv("BH_NO_SMALL"))
+    return deal_shards(j, next_dev(devs), n, 1, out, [&](bh_job* j, Dev& d, size_t, size_t) {
+      return enqueue_small(j, d, curve, SrcPlain{reinterpret_cast<const bh_batch*>(b)}, 0, n,
+                           flags);
+    });
+  return deal_shards(j, devs, n, host_shards(), out, [&](bh_job* j, Dev& d, size_t lo, size_t len) {
+    return enqueue_part(j, d, curve, b, lo, len, flags);
+  });
 }
 
 template <class B>
@@ -1838,7 +1831,7 @@ int host_verify(int curve, const B* b, size_t n, uint32_t flags, uint8_t* bitmap
   return wait_job(j);
 }
 
-// Staged host batch (bh_batch_verify*): shards as submit_job deals them, each
+// Staged host batch (bh_batch_verify*): shards as deal_shards deals them, each
 // packed into its slot's page-locked buffers by pack.h; small batches take the
 // latency path (which packs on the host anyway).
 template <class Src>
@@ -1847,36 +1840,15 @@ int submit_staged(int curve, const Src& src, size_t n, uint32_t flags, uint8_t* 
   *out = nullptr;
   std::vector<Dev*> devs = all_devs();
   if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
-  bh_job* j = new bh_job();
-  j->bitmap = bitmap;
-  j->reason = reason;
-  j->n = n;
-  if (n) std::memset(bitmap, 0, (n + 7) / 8);
-  const bool small = curve == BH_CURVE_P256 && n && n <= kSmallMax &&
-                     !(flags & BH_F_KEEP_KEYS) && !getenv("BH_NO_SMALL");
-  size_t per = 1;
-  if (const char* e = getenv("BH_HOST_SHARDS")) per = (size_t)std::max(1, std::min(atoi(e), 8));
-  const size_t nd = small ? 1 : bh::shard_devices(n, devs.size() * per);
-  static std::atomic<uint32_t> rr{0};
-  const size_t first = small ? rr++ % devs.size() : 0;
-  for (size_t k = 0; k < nd; k++) {
-    const bh::Shard sh = small ? bh::Shard{0, n} : bh::shard_of(n, nd, k);
-    if (!sh.len) break;
-    Dev& d = *devs[(first + k) % devs.size()];
-    int rc;
-    {
-      std::lock_guard<std::mutex> g(d.mu);
-      rc = small ? enqueue_small(j, d, curve, src, 0, n, flags)
-                 : enqueue_staged(j, d, curve, src, sh.lo, sh.len, flags);
-    }
-    if (rc) {
-      const std::string err = g_err;
-      (void)wait_job(j);
-      return fail(rc, err);
-    }
-  }
-  *out = j;
-  return BH_OK;
+  bh_job* j = new_job(bitmap, reason, n);
+  if (curve == BH_CURVE_P256 && n && n <= kSmallMax && !(flags & BH_F_KEEP_KEYS) &&
+      !getenv("BH_NO_SMALL"))
+    return deal_shards(j, next_dev(devs), n, 1, out, [&](bh_job* j, Dev& d, size_t, size_t) {
+      return enqueue_small(j, d, curve, src, 0, n, flags);
+    });
+  return deal_shards(j, devs, n, host_shards(), out, [&](bh_job* j, Dev& d, size_t lo, size_t len) {
+    return enqueue_staged(j, d, curve, src, lo, len, flags);
+  });
 }
 
 // Entry point `fn` does not take `curve` (it serves BH_CURVE_P256 only).
@@ -2054,6 +2026,73 @@ int p384_comb_setup(Dev& d, size_t m, bh::Comb384* cb, size_t* zero_bytes, size_
   return BH_OK;
 }
 
+// The registry as a pass sees it: nothing registered is no registry (no
+// lookup, no registry route).
+bh::KeyReg384 reg384_live(const Dev& d) {
+  bh::KeyReg384 g = d.reg384;
+  if (!d.reg384_count) g.cap = 0;
+  return g;
+}
+
+// One pass of m records (in) on stream s over the device's one P-384
+// workspace, which grows only with nothing in flight; comb: a
+// BH_F_BATCH_KEYS pass. t: the pass is waited for and its stage times and
+// route counts are added to *t. Caller holds d.mu, device set, and has ordered
+// s behind whatever used the workspace before.
+int run_pass384(Dev& d, const bh::In384& in, size_t m, bool comb, uint64_t* bitmap,
+                uint8_t* reason, hipStream_t s, bh_timing* t) {
+  bh::Pass384 p{};
+  p.in = in;
+  if (ws384_bytes(round64(m)) > d.ws384.cap) HIPCHK(hipDeviceSynchronize());
+  if (int rc = p384_setup(d, m, &p.w, &p.pl)) return rc;
+  if (comb) {  // the pass groups its records by key and plans three routes
+    const size_t nk = in.key_idx ? in.kt.nk : 0;
+    if (comb384_bytes(round64(m), nk) > d.comb384.cap) HIPCHK(hipDeviceSynchronize());
+    if (int rc = p384_comb_setup(d, m, &p.cb, &p.zero_bytes, nk)) return rc;
+  }
+  p.reg = reg384_live(d);  // keys registered: the pass plans the registry's table route
+  p.gtab = d.gtab384;
+  p.gcomb = d.gcomb384;
+  p.n = (uint32_t)m;
+  p.bitmap = bitmap;
+  p.reason = reason;
+  hipEvent_t* ev = d.ev384;
+  HIPCHK(bh::launch_pass384(p, s, d.aux, d.fork, d.join, t ? ev : nullptr));
+  if (!t) return BH_OK;
+  HIPCHK(hipEventSynchronize(ev[bh::kEv384End]));
+  auto span = [&](int a, int b, float* ms) { return hipEventElapsedTime(ms, ev[a], ev[b]); };
+  float prep, inv;
+  HIPCHK(span(bh::kEv384Start, bh::kEv384Prep, &prep));
+  HIPCHK(span(bh::kEv384Prep, bh::kEv384Inv, &inv));
+  t->prep_ms += prep;
+  t->inv_ms += inv;
+  if (!comb && !p.reg.cap) {  // the ladder over every record
+    float lad;
+    HIPCHK(span(bh::kEv384Inv, bh::kEv384End, &lad));
+    t->build_ladder_ms += lad;
+    t->n_ladder += (uint32_t)m;
+    return BH_OK;
+  }
+  // the routes start together after the plan and overlap: keycomb_ms and
+  // build_ladder_ms are each side's own time from there. A comb pass builds
+  // its tables on aux beside the ladder, the table routes behind the build.
+  float plan, routes, lad, build = 0;
+  HIPCHK(span(bh::kEv384Inv, bh::kEv384Plan, &plan));
+  HIPCHK(span(comb ? bh::kEv384Build : bh::kEv384Plan, bh::kEv384Routes, &routes));
+  HIPCHK(span(bh::kEv384Plan, bh::kEv384Ladder, &lad));
+  if (comb) HIPCHK(span(bh::kEv384Plan, bh::kEv384Build, &build));
+  uint32_t cnt[2] = {0, 0}, ctr[2] = {0, 0};  // registry route, ladder | combs wanted, comb route
+  HIPCHK(hipMemcpy(cnt, p.pl.cnt, 8, hipMemcpyDeviceToHost));
+  if (comb) HIPCHK(hipMemcpy(ctr, p.cb.ctr, 8, hipMemcpyDeviceToHost));
+  t->plan_ms += plan;
+  t->keycomb_ms += routes;
+  t->build_ladder_ms += lad + build;
+  t->n_keycomb += cnt[0] + ctr[1];
+  t->n_ladder += (uint32_t)m - cnt[0] - ctr[1];
+  if (comb) t->n_keytables += std::min(ctr[0], p.cb.cap);
+  return BH_OK;
+}
+
 // The P-384 passes of a device-resident batch on stream s, after every lane's
 // work (one workspace per device). Caller holds d.mu, device set, and counts
 // the batch for bh_device_stats (one per call of the C ABI). msg2_off /
@@ -2065,87 +2104,16 @@ int run_dev384(Dev& d, const bh_batch* b, size_t n, uint32_t flags, uint64_t* bi
   const size_t chunk = p384_chunk();
   for (size_t base = 0; base < n; base += chunk) {
     const size_t m = std::min(chunk, n - base);
-    bh::Work384 w;
-    bh::Plan384 pl;
     // the workspace may be reallocated: everything that used it has to be done
     if (int rc = sync_lanes(d)) return rc;
-    if (ws384_bytes(round64(m)) > d.ws384.cap) HIPCHK(hipDeviceSynchronize());
-    if (int rc = p384_setup(d, m, &w, &pl)) return rc;
-    bh::Comb384 cb{};
-    size_t cb_zero = 0;
-    if (flags & BH_F_BATCH_KEYS) {
-      if (comb384_bytes(round64(m)) > d.comb384.cap) HIPCHK(hipDeviceSynchronize());
-      if (int rc = p384_comb_setup(d, m, &cb, &cb_zero)) return rc;
-    }
     HIPCHK(wait_lanes(d, s));
     const bh::In384 in{b->pub + base * 96, b->sig,     b->sig_off + base, b->sig_len + base,
                        b->msg,             b->msg_off + base, b->msg_len + base,
                        flags & (BH_F_HASH_SHA256 | BH_F_NO_LOW_S | BH_F_HASH_SHA3_256),
                        msg2_off ? msg2_off + base : nullptr, msg2_len ? msg2_len + base : nullptr};
-    if (flags & BH_F_BATCH_KEYS) {  // each chunk groups its records and plans three routes
-      bh::KeyReg384 reg = d.reg384;
-      if (!d.reg384_count) reg.cap = 0;  // nothing registered: no lookup, no registry route
-      HIPCHK(bh::launch_verify384_comb(in, w, reg, d.reg384_count != 0, cb, cb.ctr, cb_zero, pl,
-                                       d.gtab384, d.gcomb384, (uint32_t)m, bitmap + base / 64,
-                                       reason + base, s, d.aux, d.fork, d.join,
-                                       t ? d.ev384 : nullptr));
-      if (t) {
-        HIPCHK(hipEventSynchronize(d.ev384[6]));
-        // after the plan (ev384[3]) the ladder runs on s beside the comb build
-        // and, behind it (ev384[7]), the table routes on aux
-        float ms[6];
-        for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], d.ev384[k], d.ev384[k + 1]));
-        HIPCHK(hipEventElapsedTime(&ms[3], d.ev384[7], d.ev384[4]));
-        HIPCHK(hipEventElapsedTime(&ms[4], d.ev384[3], d.ev384[5]));
-        HIPCHK(hipEventElapsedTime(&ms[5], d.ev384[3], d.ev384[7]));
-        uint32_t cnt[2] = {0, 0}, ctr[2] = {0, 0};
-        HIPCHK(hipMemcpy(cnt, pl.cnt, 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ctr, cb.ctr, 8, hipMemcpyDeviceToHost));
-        t->prep_ms += ms[0];
-        t->inv_ms += ms[1];
-        t->plan_ms += ms[2];
-        t->keycomb_ms += ms[3];
-        t->build_ladder_ms += ms[4] + ms[5];
-        t->n_keycomb += cnt[0] + ctr[1];
-        t->n_ladder += (uint32_t)m - cnt[0] - ctr[1];
-        t->n_keytables += std::min(ctr[0], cb.cap);
-      }
-      continue;
-    }
-    if (d.reg384_count) {  // keys registered: each chunk plans its own two routes
-      HIPCHK(bh::launch_verify384_keys(in, w, d.reg384, pl, d.gtab384, (uint32_t)m,
-                                       bitmap + base / 64, reason + base, s, d.aux, d.fork,
-                                       d.join, t ? d.ev384 : nullptr));
-      if (t) {
-        HIPCHK(hipEventSynchronize(d.ev384[6]));
-        // the two routes start together after the plan (ev384[3]) and overlap:
-        // keycomb_ms and build_ladder_ms are each route's own time from there
-        float ms[5];
-        for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[k], d.ev384[k], d.ev384[k + 1]));
-        HIPCHK(hipEventElapsedTime(&ms[4], d.ev384[3], d.ev384[5]));
-        uint32_t cnt[2] = {0, 0};
-        HIPCHK(hipMemcpy(cnt, pl.cnt, 8, hipMemcpyDeviceToHost));
-        t->prep_ms += ms[0];
-        t->inv_ms += ms[1];
-        t->plan_ms += ms[2];
-        t->keycomb_ms += ms[3];
-        t->build_ladder_ms += ms[4];
-        t->n_keycomb += cnt[0];
-        t->n_ladder += (uint32_t)m - cnt[0];
-      }
-      continue;
-    }
-    HIPCHK(bh::launch_verify384(in, w, d.gtab384, (uint32_t)m, bitmap + base / 64, reason + base,
-                                s, t ? d.ev384 : nullptr));
-    if (t) {
-      HIPCHK(hipEventSynchronize(d.ev384[3]));
-      float ms[3];
-      for (int k = 0; k < 3; k++) HIPCHK(hipEventElapsedTime(&ms[k], d.ev384[k], d.ev384[k + 1]));
-      t->prep_ms += ms[0];
-      t->inv_ms += ms[1];
-      t->build_ladder_ms += ms[2];
-      t->n_ladder += (uint32_t)m;
-    }
+    if (int rc = run_pass384(d, in, m, (flags & BH_F_BATCH_KEYS) != 0, bitmap + base / 64,
+                             reason + base, s, t))
+      return rc;
   }
   HIPCHK(hipEventRecord(d.done, s));
   d.done_recorded = true;
@@ -2336,8 +2304,8 @@ int host_verify_chunked(int curve, const bh_batch* b, size_t n, uint32_t flags, 
 
 // ---- P-384 BatchVerify: compact keys, pipelined jobs, every device ---------------
 // bh_verify384_compact(_submit) and bh_batch_verify384_ptrs(_submit). A batch
-// is dealt over the devices in 64-aligned shards as submit_job deals them; a
-// shard is packed into one of its device's two Slot384s (page-locked), uploaded
+// is dealt over the devices in 64-aligned shards as deal_shards deals them; a
+// shard is packed into one of its device's two P-384 StageSlots (page-locked), uploaded
 // on the copy stream, and run on the device's P-384 stream behind every lane's
 // work: the shard's distinct keys are imported once (k384_keys_prep), then its
 // chunks of BH_P384_CHUNK records pass one after the other over the device's
@@ -2389,23 +2357,7 @@ Lay384 lay384(size_t m, size_t nk_cap, bool indexed, size_t sig_bytes, size_t ms
   return L;
 }
 
-// Take the device's next P-384 slot, collecting the shard that still holds it
-// (caller holds d.mu).
-Slot384& take_slot384(Dev& d, int* k) {
-  *k = (int)(d.next_s384++ % kSlots384);
-  Slot384& sl = d.s384[*k];
-  if (sl.owner) {
-    bh_job* o = sl.owner;
-    int rc = finish_part(o, sl.owner_part);
-    if (rc && o->rc == BH_OK) {
-      o->rc = rc;
-      o->err = g_err;
-    }
-  }
-  return sl;
-}
-
-int ensure_slot384(Slot384& sl, const Lay384& L) {
+int ensure_slot384(StageSlot& sl, const Lay384& L) {
   int rc;
   if ((rc = sl.hin.ensure(L.total + 256))) return rc;
   if ((rc = sl.din.ensure(L.dev_total + 256))) return rc;
@@ -2417,7 +2369,7 @@ int ensure_slot384(Slot384& sl, const Lay384& L) {
 // After a shard's upload is queued on the copy stream (sl.uploaded recorded):
 // the key import and the chunks' passes on the device's P-384 stream, the
 // results into the slot's page-locked buffer. Caller holds d.mu, device set.
-int launch_shard384(bh_job* j, Dev& d, int k, Slot384& sl, const Lay384& L, size_t lo,
+int launch_shard384(bh_job* j, Dev& d, int k, StageSlot& sl, const Lay384& L, size_t lo,
                     uint32_t flags) {
   hipStream_t s = d.stream;
   const size_t m = L.m;
@@ -2426,8 +2378,6 @@ int launch_shard384(bh_job* j, Dev& d, int k, Slot384& sl, const Lay384& L, size
   uint8_t* drs = (uint8_t*)(dbm + round64(m) / 64);
   HIPCHK(hipStreamWaitEvent(s, sl.uploaded, 0));
   HIPCHK(wait_lanes(d, s));
-  bh::KeyReg384 reg = d.reg384;
-  if (!d.reg384_count) reg.cap = 0;  // nothing registered: no lookup, no registry route
   bh::Keys384 kt{};
   if (L.indexed) {  // once per shard: every chunk reads the key workspace
     kt.nk = (uint32_t)L.nk;
@@ -2436,23 +2386,11 @@ int launch_shard384(bh_job* j, Dev& d, int k, Slot384& sl, const Lay384& L, size
     kt.qy = (uint32_t*)(dv + L.o_qy);
     kt.st = (uint8_t*)(dv + L.o_kst);
     kt.slot = (uint32_t*)(dv + L.o_kslot);
-    HIPCHK(bh::launch_keys384_prep((const uint8_t*)(dv + L.o_keys), kt, reg, s));
+    HIPCHK(bh::launch_keys384_prep((const uint8_t*)(dv + L.o_keys), kt, reg384_live(d), s));
   }
   const size_t chunk = p384_chunk();
   for (size_t base = 0; base < m; base += chunk) {
     const size_t mc = std::min(chunk, m - base);
-    bh::Work384 w;
-    bh::Plan384 pl;
-    // the one workspace of the device: it grows only with nothing in flight
-    if (ws384_bytes(round64(mc)) > d.ws384.cap) HIPCHK(hipDeviceSynchronize());
-    if (int rc = p384_setup(d, mc, &w, &pl)) return rc;
-    bh::Comb384 cb{};
-    size_t cb_zero = 0;
-    if (flags & BH_F_BATCH_KEYS) {
-      const size_t nk = L.indexed ? L.nk : 0;
-      if (comb384_bytes(round64(mc), nk) > d.comb384.cap) HIPCHK(hipDeviceSynchronize());
-      if (int rc = p384_comb_setup(d, mc, &cb, &cb_zero, nk)) return rc;
-    }
     bh::In384 in{(const uint8_t*)(dv + L.o_keys) + (L.indexed ? 0 : base * 96),
                  (const uint8_t*)(dv + L.o_sig),
                  (const uint64_t*)(dv + L.o_soff) + base,
@@ -2465,18 +2403,9 @@ int launch_shard384(bh_job* j, Dev& d, int k, Slot384& sl, const Lay384& L, size
       in.key_idx = (const uint32_t*)(dv + L.o_idx) + base;
       in.kt = kt;
     }
-    if (flags & BH_F_BATCH_KEYS) {
-      HIPCHK(bh::launch_verify384_comb(in, w, reg, d.reg384_count != 0, cb, cb.ctr, cb_zero, pl,
-                                       d.gtab384, d.gcomb384, (uint32_t)mc, dbm + base / 64,
-                                       drs + base, s, d.aux, d.fork, d.join, nullptr));
-    } else if (d.reg384_count) {
-      HIPCHK(bh::launch_verify384_keys(in, w, d.reg384, pl, d.gtab384, (uint32_t)mc,
-                                       dbm + base / 64, drs + base, s, d.aux, d.fork, d.join,
-                                       nullptr));
-    } else {
-      HIPCHK(bh::launch_verify384(in, w, d.gtab384, (uint32_t)mc, dbm + base / 64, drs + base, s,
-                                  nullptr));
-    }
+    if (int rc = run_pass384(d, in, mc, (flags & BH_F_BATCH_KEYS) != 0, dbm + base / 64,
+                             drs + base, s, nullptr))
+      return rc;
   }
   // a kernel, not a D2H copy, for launch_part's reason: the copy engine's next
   // command is the other slot's upload
@@ -2484,11 +2413,7 @@ int launch_shard384(bh_job* j, Dev& d, int k, Slot384& sl, const Lay384& L, size
   HIPCHK(hipEventRecord(sl.done, s));
   HIPCHK(hipEventRecord(d.done, s));
   d.done_recorded = true;
-  sl.owner = j;
-  sl.owner_part = j->parts.size();
-  Part part{&d, k, lo, m, false};
-  part.p384 = true;
-  j->parts.push_back(part);
+  bind_owner(sl, j, Part{&d, k, lo, m, false, PartKind::p384});
   return BH_OK;
 }
 
@@ -2500,7 +2425,7 @@ int enqueue384_compact(bh_job* j, Dev& d, const bh_cbatch& c, size_t lo, size_t 
                        uint64_t* mb) {
   HIPCHK(hipSetDevice(d.id));
   int k;
-  Slot384& sl = take_slot384(d, &k);
+  StageSlot& sl = take_slot(d.s384, d.next_s384, &k);
   uint64_t sbytes = 0, mbytes = 0;
   for (size_t i = lo; i < lo + m; i++) {
     sbytes += c.sig_len[i];
@@ -2549,16 +2474,6 @@ int enqueue384_compact(bh_job* j, Dev& d, const bh_cbatch& c, size_t lo, size_t 
   return launch_shard384(j, d, k, sl, L, lo, flags);
 }
 
-const uint8_t kZeroKey384[96] = {0};
-struct SrcPtrs384 {  // SrcPtrs with 96-byte keys
-  const bh_pbatch* b;
-  const uint8_t* key(size_t i) const { return b->pub[i] ? b->pub[i] : kZeroKey384; }
-  const uint8_t* sig(size_t i) const { return b->sig[i]; }
-  uint32_t sig_len(size_t i) const { return b->sig[i] ? b->sig_len[i] : 0u; }
-  const uint8_t* msg(size_t i) const { return b->msg[i]; }
-  uint32_t msg_len(size_t i) const { return b->msg[i] ? b->msg_len[i] : 0u; }
-};
-
 // the 96-byte packer (its own worker pool, made at the first staged P-384 batch)
 std::mutex g_pack384_mu;
 bh::pack::PackerT<96>& packer384() {
@@ -2570,11 +2485,11 @@ bh::pack::PackerT<96>& packer384() {
 // the slot's page-locked staging: keys de-duplicated by content, the bytes'
 // chunks uploaded as each completes, then the keys, indices, offsets and
 // lengths. Everything is copied when this returns. Caller holds d.mu.
-int enqueue384_staged(bh_job* j, Dev& d, const SrcPtrs384& src, size_t lo, size_t m,
+int enqueue384_staged(bh_job* j, Dev& d, const SrcPtrs<96>& src, size_t lo, size_t m,
                       uint32_t flags) {
   HIPCHK(hipSetDevice(d.id));
   int k;
-  Slot384& sl = take_slot384(d, &k);
+  StageSlot& sl = take_slot(d.s384, d.next_s384, &k);
   std::lock_guard<std::mutex> pg(g_pack384_mu);
   bh::pack::PackerT<96>& P = packer384();
   bh::pack::Result r;
@@ -2612,44 +2527,20 @@ int enqueue384_staged(bh_job* j, Dev& d, const SrcPtrs384& src, size_t lo, size_
 }
 
 // The shards of a P-384 batch over all initialised devices, BH_HOST_SHARDS per
-// device, dealt as submit_job deals them; enq(j, d, lo, len) under d.mu. One
+// device (deal_shards); enq(j, d, lo, len) under d.mu. One
 // batch for bh_device_stats, however many shards and chunks.
 template <class Enq>
 int submit384(size_t n, uint8_t* bitmap, uint8_t* reason, bh_job** out, Enq enq) {
   *out = nullptr;
   std::vector<Dev*> devs = all_devs();
   if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
-  bh_job* j = new bh_job();
-  j->bitmap = bitmap;
-  j->reason = reason;
-  j->n = n;
+  bh_job* j = new_job(bitmap, reason, n);
   if (n) {
-    std::memset(bitmap, 0, (n + 7) / 8);
     g_dev_batches.fetch_add(1, std::memory_order_relaxed);
     g_dev_records.fetch_add(n, std::memory_order_relaxed);
   }
-  static const size_t per = [] {  // read once, like BH_P384_CHUNK
-    const char* e = getenv("BH_HOST_SHARDS");
-    return e ? (size_t)std::max(1, std::min(atoi(e), 8)) : size_t(1);
-  }();
-  const size_t nd = bh::shard_devices(n, devs.size() * per);
-  for (size_t k = 0; k < nd; k++) {
-    const bh::Shard sh = bh::shard_of(n, nd, k);
-    if (!sh.len) break;
-    Dev& d = *devs[k % devs.size()];
-    int rc;
-    {
-      std::lock_guard<std::mutex> g(d.mu);
-      rc = enq(j, d, sh.lo, sh.len);
-    }
-    if (rc) {
-      const std::string err = g_err;
-      (void)wait_job(j);  // drain what was enqueued
-      return fail(rc, err);
-    }
-  }
-  *out = j;
-  return BH_OK;
+  static const size_t per = host_shards();  // read once, like BH_P384_CHUNK
+  return deal_shards(j, devs, n, per, out, enq);
 }
 
 // device >= 0: that device; -1: every initialised device.
@@ -2657,7 +2548,7 @@ int submit384(size_t n, uint8_t* bitmap, uint8_t* reason, bh_job** out, Enq enq)
 int hash_setup(Dev& d) {
   if (d.hstream) return BH_OK;
   HIPCHK(hipStreamCreateWithFlags(&d.hstream, hipStreamNonBlocking));
-  for (HashSlot& sl : d.hslot)
+  for (StageSlot& sl : d.hslot)
     HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming |
                                                  (blocking_sync() ? hipEventBlockingSync : 0u)));
   return BH_OK;
@@ -2699,16 +2590,8 @@ int enqueue_hash(bh_job* j, Dev& d, int alg, const bh_hbatch* b, size_t n) {
   HIPCHK(hipSetDevice(d.id));
   int rc;
   if ((rc = hash_setup(d))) return rc;
-  const int k = (int)(d.next_hslot++ % kHashSlots);
-  HashSlot& sl = d.hslot[k];
-  if (sl.owner) {  // the slot still holds an uncollected job: collect it now
-    bh_job* o = sl.owner;
-    rc = finish_part(o, sl.owner_part);
-    if (rc && o->rc == BH_OK) {
-      o->rc = rc;
-      o->err = g_err;
-    }
-  }
+  int k;
+  StageSlot& sl = take_slot(d.hslot, d.next_hslot, &k);
   hipStream_t s = d.hstream;
   const bool want = b->want_off != nullptr;
   const size_t ns = n * b->nspan;
@@ -2765,11 +2648,7 @@ int enqueue_hash(bh_job* j, Dev& d, int alg, const bh_hbatch* b, size_t n) {
   if (ddig) HIPCHK(bh::launch_result_out(ddig, sl.hout.p, n * 32, s));
   if (dres) HIPCHK(bh::launch_result_out(dres, (uint8_t*)sl.hout.p + o_res, n, s));
   HIPCHK(hipEventRecord(sl.done, s));
-  sl.owner = j;
-  sl.owner_part = j->parts.size();
-  Part part{&d, k, 0, n, false};
-  part.hash = true;
-  j->parts.push_back(part);
+  bind_owner(sl, j, Part{&d, k, 0, n, false, PartKind::hash});
   return BH_OK;
 }
 
@@ -2779,25 +2658,13 @@ int submit_hash(int alg, const bh_hbatch* b, size_t n, uint8_t* digest, uint8_t*
   if (int rc = check_hash(alg, b, n, digest, result, true)) return rc;
   std::vector<Dev*> devs = all_devs();
   if (devs.empty()) return fail(BH_E_NOT_INIT, "bh_init not called");
-  bh_job* j = new bh_job();
+  bh_job* j = new_job(nullptr, nullptr, n);
   j->digest = digest;
   j->hresult = result;
-  j->n = n;
-  if (n) {
-    Dev& d = *devs[0];
-    int rc;
-    {
-      std::lock_guard<std::mutex> g(d.mu);
-      rc = enqueue_hash(j, d, alg, b, n);
-    }
-    if (rc) {
-      const std::string err = g_err;
-      (void)wait_job(j);  // drain what was enqueued
-      return fail(rc, err);
-    }
-  }
-  *out = j;
-  return BH_OK;
+  // the first device alone, the batch whole
+  return deal_shards(j, {devs[0]}, n, 1, out, [&](bh_job* j, Dev& d, size_t, size_t) {
+    return enqueue_hash(j, d, alg, b, n);
+  });
 }
 
 int for_devices(int device, const std::function<int(Dev&)>& fn) {
@@ -3483,7 +3350,7 @@ int bh_batch_verify_ptrs_submit(int curve, const bh_pbatch* b, size_t n, uint32_
                    !reason)))
     return fail(BH_E_INVALID, "null pointer in batch");
   if (int rc = check_staged(curve, flags, n)) return rc;
-  return submit_staged(curve, SrcPtrs{b}, n, flags, bitmap, reason, job);
+  return submit_staged(curve, SrcPtrs<64>{b}, n, flags, bitmap, reason, job);
 }
 
 int bh_batch_verify_ptrs(int curve, const bh_pbatch* b, size_t n, uint32_t flags,
@@ -3544,7 +3411,7 @@ int bh_batch_verify384_ptrs_submit(const bh_pbatch* b, size_t n, uint32_t flags,
     return fail(BH_E_INVALID, "null pointer in batch");
   if (int rc = check_flags(flags, "bh_batch_verify384_ptrs")) return rc;
   if (n > 0xffffffffull) return fail(BH_E_INVALID, "batch too large");
-  const SrcPtrs384 src{b};
+  const SrcPtrs<96> src{b};
   return submit384(n, bitmap, reason, job, [&](bh_job* j, Dev& d, size_t lo, size_t len) {
     return enqueue384_staged(j, d, src, lo, len, flags);
   });

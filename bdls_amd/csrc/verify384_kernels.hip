@@ -36,7 +36,14 @@
 //   k384_comb_group_idx   1 lane/record   one atomic addition on cnt[key_idx[i]]
 //   k384_comb_assign_idx  1 lane/key      registry, comb slot or ladder
 //   k384_comb_bases_idx   1 lane/comb     the chain from the key workspace
-#include "comb384.h"
+//
+// The host's entry points (namespace bh, at the end of the file):
+//   launch_gtab384_build     k384_gtab
+//   launch_comb384_g         k384_comb_g
+//   launch_pass384           one pass by any of the three routes above (pass384.h)
+//   launch_keys384_prep      k384_keys_prep
+//   launch_keys384_register  the four registration kernels
+#include "pass384.h"
 
 using namespace bh;
 
@@ -315,116 +322,83 @@ hipError_t launch_gtab384_build(uint32_t* gtab, hipStream_t s) {
   return hipGetLastError();
 }
 
-// ev (optional): 4 events around prep, inverse, ladder + bitmap.
-hipError_t launch_verify384(const In384& in, const Work384& w, const uint32_t* gtab, uint32_t n,
-                            uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipEvent_t* ev) {
-  if (n == 0) return hipSuccess;
-  hipError_t e;
-  const dim3 blk(64), grd((n + 63) / 64);
-  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_prep, grd, blk, 0, s, in, w, n);
-  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
-  const uint32_t stride = (n + kInvChunk384 - 1) / kInvChunk384;
-  hipLaunchKernelGGL(k384_inv, dim3((stride + 63) / 64), blk, 0, s, w, stride, n);
-  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_ladder, grd, blk, 0, s, w, gtab, n, reason);
-  hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
-  if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
-  return hipGetLastError();
-}
-
-// The pass with keys in the registry. pl.cnt is cleared here; the list kernels
-// are launched for n lanes and read their list's length on the device. The two
-// routes run side by side: the table route on aux (fork / join order it after
-// the plan and before the bitmap), the ladder on s, whose one wave per SIMD
-// leaves registers for the table route's waves.
-// ev (optional): 7 events: prep, inverse, plan | end of the table route (on
-// aux) | end of the ladder (on s) | end of the bitmap.
-hipError_t launch_verify384_keys(const In384& in, const Work384& w, const KeyReg384& g,
-                                 const Plan384& pl, const uint32_t* gtab, uint32_t n,
-                                 uint64_t* bitmap, uint8_t* reason, hipStream_t s, hipStream_t aux,
-                                 hipEvent_t fork, hipEvent_t join, hipEvent_t* ev) {
-  if (n == 0) return hipSuccess;
-  hipError_t e;
-  const dim3 blk(64), grd((n + 63) / 64);
-  if ((e = hipMemsetAsync(pl.cnt, 0, 8, s)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_prep, grd, blk, 0, s, in, w, n);
-  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
-  const uint32_t stride = (n + kInvChunk384 - 1) / kInvChunk384;
-  hipLaunchKernelGGL(k384_inv, dim3((stride + 63) / 64), blk, 0, s, w, stride, n);
-  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_plan, grd, blk, 0, s, in, w, g, n, pl);
-  if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
-  if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_keywin, grd, blk, 0, aux, w, g, pl, gtab, reason);
-  if (ev && (e = hipEventRecord(ev[4], aux)) != hipSuccess) return e;
-  if ((e = hipEventRecord(join, aux)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_ladder_list, grd, blk, 0, s, w, pl, gtab, reason);
-  if (ev && (e = hipEventRecord(ev[5], s)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
-  if (ev && (e = hipEventRecord(ev[6], s)) != hipSuccess) return e;
-  return hipGetLastError();
-}
-
 // The comb of G into gcomb (kComb384Words), with a comb slot's bases and side as scratch.
 hipError_t launch_comb384_g(uint32_t* bases, uint32_t* side, uint32_t* gcomb, hipStream_t s) {
   hipLaunchKernelGGL(k384_comb_g, dim3(1), dim3(64), 0, s, bases, side, gcomb);
   return hipGetLastError();
 }
 
-// The pass with BH_F_BATCH_KEYS. zero / zero_bytes: cb's per-pass counters and
-// buckets (ctr, rep, cnt, contiguous), cleared here with pl.cnt. After the
-// inverse the records are grouped and routed; then, side by side, the ladder
-// list on s and on aux the comb build, the comb route and (with_reg: the
-// registry is not empty) the registry's table route. The list kernels are
-// launched for n lanes, the build kernels for cb.cap, and read their counts on
-// the device.
-// ev (optional): 8 events: prep, inverse, group + plan | end of the table
-// routes (on aux) | end of the ladder (on s) | end of the bitmap | ev[7]: end
-// of the comb build (on aux, before the table routes).
-hipError_t launch_verify384_comb(const In384& in, const Work384& w, const KeyReg384& g,
-                                 bool with_reg, const Comb384& cb, void* zero, size_t zero_bytes,
-                                 const Plan384& pl, const uint32_t* gtab, const uint32_t* gcomb,
-                                 uint32_t n, uint64_t* bitmap, uint8_t* reason, hipStream_t s,
-                                 hipStream_t aux, hipEvent_t fork, hipEvent_t join, hipEvent_t* ev) {
+// One pass of p.n records on s; its route follows from p (pass384.h).
+//
+// The ladder alone (no comb, p.reg.cap == 0): prep, inverse, k384_ladder over
+// all n records, bitmap.
+//
+// With keys in the registry, or with BH_F_BATCH_KEYS: p.pl.cnt is cleared here
+// (a comb pass: cb's per-pass counters and buckets, contiguous from cb.ctr,
+// too). After the inverse the records are planned -- a comb pass groups them by
+// key first -- into index lists; then, side by side, the ladder list on s,
+// whose one wave per SIMD leaves registers for the table routes' waves, and on
+// aux (fork / join order it after the plan and before the bitmap) the comb
+// build and the comb route of a comb pass and, with p.reg.cap != 0, the
+// registry's table route. The list kernels are launched for n lanes, the build
+// kernels for cb.cap, and read their counts on the device.
+//
+// ev (optional): the events of Ev384 that the route has.
+hipError_t launch_pass384(const Pass384& p, hipStream_t s, hipStream_t aux, hipEvent_t fork,
+                          hipEvent_t join, hipEvent_t* ev) {
+  const uint32_t n = p.n;
   if (n == 0) return hipSuccess;
+  const In384& in = p.in;
+  const Work384& w = p.w;
+  const Plan384& pl = p.pl;
+  const Comb384& cb = p.cb;
+  const bool comb = cb.tables != nullptr, routed = comb || p.reg.cap != 0;
   hipError_t e;
+  auto mark = [&](Ev384 k, hipStream_t on) { return ev ? hipEventRecord(ev[k], on) : hipSuccess; };
   const dim3 blk(64), grd((n + 63) / 64), grdk((cb.cap + 63) / 64);
-  if ((e = hipMemsetAsync(pl.cnt, 0, 8, s)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(zero, 0, zero_bytes, s)) != hipSuccess) return e;
-  if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
+  if (routed && (e = hipMemsetAsync(pl.cnt, 0, 8, s)) != hipSuccess) return e;
+  if (comb && (e = hipMemsetAsync(cb.ctr, 0, p.zero_bytes, s)) != hipSuccess) return e;
+  if ((e = mark(kEv384Start, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(k384_prep, grd, blk, 0, s, in, w, n);
-  if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
+  if ((e = mark(kEv384Prep, s)) != hipSuccess) return e;
   const uint32_t stride = (n + kInvChunk384 - 1) / kInvChunk384;
   hipLaunchKernelGGL(k384_inv, dim3((stride + 63) / 64), blk, 0, s, w, stride, n);
-  if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
-  if (in.key_idx) {  // grouped by key index (cb.hc >= in.kt.nk)
-    hipLaunchKernelGGL(k384_comb_group_idx, grd, blk, 0, s, in, w, cb, n);
-    hipLaunchKernelGGL(k384_comb_assign_idx, dim3((in.kt.nk + 63) / 64), blk, 0, s, in, cb);
+  if ((e = mark(kEv384Inv, s)) != hipSuccess) return e;
+  if (!routed) {
+    hipLaunchKernelGGL(k384_ladder, grd, blk, 0, s, w, p.gtab, n, p.reason);
   } else {
-    hipLaunchKernelGGL(k384_comb_group, grd, blk, 0, s, in, w, cb, n);
-    hipLaunchKernelGGL(k384_comb_assign, grd, blk, 0, s, in, g, cb, n);
+    if (!comb) {
+      hipLaunchKernelGGL(k384_plan, grd, blk, 0, s, in, w, p.reg, n, pl);
+    } else {
+      if (in.key_idx) {  // grouped by key index (cb.hc >= in.kt.nk)
+        hipLaunchKernelGGL(k384_comb_group_idx, grd, blk, 0, s, in, w, cb, n);
+        hipLaunchKernelGGL(k384_comb_assign_idx, dim3((in.kt.nk + 63) / 64), blk, 0, s, in, cb);
+      } else {
+        hipLaunchKernelGGL(k384_comb_group, grd, blk, 0, s, in, w, cb, n);
+        hipLaunchKernelGGL(k384_comb_assign, grd, blk, 0, s, in, p.reg, cb, n);
+      }
+      hipLaunchKernelGGL(k384_comb_plan, grd, blk, 0, s, cb, n, pl);
+    }
+    if ((e = mark(kEv384Plan, s)) != hipSuccess) return e;
+    if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
+    if (comb) {
+      if (in.key_idx) hipLaunchKernelGGL(k384_comb_bases_idx, grdk, blk, 0, aux, in, cb);
+      else hipLaunchKernelGGL(k384_comb_bases, grdk, blk, 0, aux, w, cb);
+      hipLaunchKernelGGL(k384_comb_rows, grdk, blk, 0, aux, cb);
+      if ((e = mark(kEv384Build, aux)) != hipSuccess) return e;
+      hipLaunchKernelGGL(k384_comb, grd, blk, 0, aux, w, cb, pl, p.gcomb, p.reason);
+    }
+    if (p.reg.cap)
+      hipLaunchKernelGGL(k384_keywin, grd, blk, 0, aux, w, p.reg, pl, p.gtab, p.reason);
+    if ((e = mark(kEv384Routes, aux)) != hipSuccess) return e;
+    if ((e = hipEventRecord(join, aux)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k384_ladder_list, grd, blk, 0, s, w, pl, p.gtab, p.reason);
+    if ((e = mark(kEv384Ladder, s)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k384_comb_plan, grd, blk, 0, s, cb, n, pl);
-  if (ev && (e = hipEventRecord(ev[3], s)) != hipSuccess) return e;
-  if ((e = hipEventRecord(fork, s)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(aux, fork, 0)) != hipSuccess) return e;
-  if (in.key_idx) hipLaunchKernelGGL(k384_comb_bases_idx, grdk, blk, 0, aux, in, cb);
-  else hipLaunchKernelGGL(k384_comb_bases, grdk, blk, 0, aux, w, cb);
-  hipLaunchKernelGGL(k384_comb_rows, grdk, blk, 0, aux, cb);
-  if (ev && (e = hipEventRecord(ev[7], aux)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_comb, grd, blk, 0, aux, w, cb, pl, gcomb, reason);
-  if (with_reg) hipLaunchKernelGGL(k384_keywin, grd, blk, 0, aux, w, g, pl, gtab, reason);
-  if (ev && (e = hipEventRecord(ev[4], aux)) != hipSuccess) return e;
-  if ((e = hipEventRecord(join, aux)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_ladder_list, grd, blk, 0, s, w, pl, gtab, reason);
-  if (ev && (e = hipEventRecord(ev[5], s)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(s, join, 0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, reason, n, bitmap);
-  if (ev && (e = hipEventRecord(ev[6], s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k384_bitmap, dim3((n + 255) / 256), dim3(256), 0, s, p.reason, n, p.bitmap);
+  if ((e = mark(kEv384End, s)) != hipSuccess) return e;
   return hipGetLastError();
 }
 
